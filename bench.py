@@ -7,11 +7,15 @@ per GPU, fp32 (weak scaling: global batch = 32 * n_gpus; 8 GPUs = configs[2]'s g
 batch 256).  One "step" = one reference iteration (GLI:560-714): D step (D(real), G(z)
 no-grad, D(fake), head, backward, Adam) + G step (G(z), D(fake), fresh real batch D(x),
 head, backward, Adam).  Inputs are resident in HBM (a 1024-image synthetic set; batches
-gathered on the device, z drawn on the device).  On one GPU the line also carries the
-64^2 half of the metric (C1: RaLSGAN 64^2, B=32, h=128 = configs[0]'s shape) and
-configs[1] (C2: RaSGAN 128^2, B=64) under ``extra_workloads``.
+gathered on the device, z drawn on the device).
 
-Prints ONE JSON line (rank 0).  Extra fields:
+A plain run (``bench.py --gpus 1 --steps K --warmup W``) sets up, warms up, times the K
+steps and prints ONE JSON line (rank 0) with the headline figure: ``value`` (images/s) and
+``ms_per_step`` of the timed steps.  ``--dump-outputs DIR`` also writes what the last timed
+step left with its caller (step_outputs below) as DIR/<name>.npy.  Everything else is
+measured only with ``--full``: on one GPU the line then also carries the 64^2 half of the
+metric (C1: RaLSGAN 64^2, B=32, h=128 = configs[0]'s shape) and configs[1] (C2: RaSGAN
+128^2, B=64) under ``extra_workloads``, and the fields
   roofline     -- the dominant kernel (the fp32-MFMA implicit-GEMM conv): algorithmic
                   FLOPs / its HIP-event-timed duration over the timed region, against
                   the fp32 MFMA peak (157.3 TFLOP/s);
@@ -24,7 +28,10 @@ Prints ONE JSON line (rank 0).  Extra fields:
   dp_path_n1   -- (N=1) the workload (and C1) run exactly as each rank of an N>1 run does
                   (launch mode of the data-parallel path: eager above 50M parameters,
                   piecewise graphs below): the like-for-like baseline of the scaling runs.
-Launch: python bench.py [--gpus N --steps K --warmup W].  N>1: either under
+(``roofline`` is also there without ``--full`` in an eager run, ``--graph off`` or large models
+at N>1, which times its kernels inside the timed region, and on the data-parallel path, N>1 or
+``--force-dp``, whose piecewise graphs keep their eager iterations after the timed replays).
+Launch: python bench.py [--gpus N --steps K --warmup W] [--full] [--dump-outputs DIR].  N>1: either under
 ``torch.distributed.run --nproc-per-node N`` (WORLD_SIZE must equal N), or plain
 ``python bench.py --gpus N``, which starts the N ranks itself (torch.distributed.run as a
 child process, before anything touches the GPU) and relays rank 0's line (the
@@ -181,9 +188,43 @@ def restatement_check():
     return out
 
 
-def run_workload(name, steps, warmup, world, args, K, emu=False, dp_path=False, host_rng=False):
+DUMP_SAMPLE = 65536   # elements kept of each larger state tensor (--dump-outputs)
+
+
+def step_outputs(t):
+    """What the last iteration left with its caller, as float32 / float64 numpy arrays: both
+    steps' losses and D outputs (Trainer.errD / errG / last) and the nets the step updated
+    (G.* / D.*: every state_dict entry; of a tensor above DUMP_SAMPLE elements a fixed, seeded
+    sample of DUMP_SAMPLE, the same indices in every run -- the headline nets hold 1.5 GB)."""
+    out = {"errD": t.errD, "errG": t.errG}
+    for side in ("D", "G"):
+        for key in ("y_pred", "y_pred_fake"):
+            v = t.last[side].get(key)
+            if v is not None:
+                out[f"{side}_step.{key}"] = v
+    g = torch.Generator().manual_seed(20240229)
+    for net, mod in (("G", t.G), ("D", t.D)):
+        for key, v in mod.state_dict().items():
+            v = v.detach().reshape(-1)
+            if v.numel() > DUMP_SAMPLE:
+                idx = torch.randint(0, v.numel(), (DUMP_SAMPLE,), generator=g).sort().values
+                v = v[idx.to(v.device)]
+            out[f"{net}.{key}"] = v
+    return {k: v.detach().to("cpu", torch.float32 if v.dtype in (torch.float32, torch.float16, torch.bfloat16)
+                             else torch.float64).numpy() for k, v in out.items()}
+
+
+def dump_outputs(folder, outputs):
+    os.makedirs(folder, exist_ok=True)
+    import numpy
+    for name, a in outputs.items():
+        numpy.save(os.path.join(folder, name + ".npy"), a)
+
+
+def run_workload(name, steps, warmup, world, args, K, emu=False, dp_path=False, host_rng=False, dump=False):
     """Train `steps` timed iterations of workload `name` (after `warmup`); returns the
-    measurement (max over ranks).  emu: forward / data-gradient GEMMs on bf16x6.  dp_path:
+    measurement (max over ranks).  dump: also return step_outputs() of the last timed
+    iteration, read right after the timed region.  emu: forward / data-gradient GEMMs on bf16x6.  dp_path:
     run one process in the launch mode every rank of an N > 1 run uses (eager above 50M
     parameters, piecewise graphs below; batched D pass as at N = 1) -- the like-for-like
     N = 1 baseline of the scaling runs.  host_rng: batches and z drawn on the host in the reference's order (numpy choice,
@@ -191,12 +232,12 @@ def run_workload(name, steps, warmup, world, args, K, emu=False, dp_path=False, 
     (a graph replay would repeat its capture's draws)."""
     prev_emu = K.set_gemm_emulation(emu)
     try:
-        return _run_workload(name, steps, warmup, world, args, K, dp_path, host_rng)
+        return _run_workload(name, steps, warmup, world, args, K, dp_path, host_rng, dump)
     finally:
         K.set_gemm_emulation(prev_emu)
 
 
-def _run_workload(name, steps, warmup, world, args, K, dp_path=False, host_rng=False):
+def _run_workload(name, steps, warmup, world, args, K, dp_path=False, host_rng=False, dump=False):
     from relativisticgan_amd.config import make_param
     from relativisticgan_amd.train import Trainer, synthetic_images
     loss_D, size, bpg, h = WORKLOADS[name]
@@ -267,18 +308,22 @@ def _run_workload(name, steps, warmup, world, args, K, dp_path=False, host_rng=F
             graph.replay()
         barrier()
         elapsed = time.perf_counter() - t0
-        # per-kernel HIP events cannot be read out of graph replays: the kernel statistics
-        # of the roofline come from eager iterations of the same step, right after
-        nprof = max(3, min(steps, 10))
-        K.profile_begin(capacity=400 * nprof + 64)
-        with torch.cuda.stream(side):
-            for i in range(nprof):
-                t.iteration(it + i)
-            t.flush()
-        torch.cuda.current_stream().wait_stream(side)
-        barrier()
-        prof = K.profile_end()
-        prof["steps"] = nprof
+        outputs = step_outputs(t) if dump else None
+        prof = None
+        if args.full or multi:
+            # per-kernel HIP events cannot be read out of graph replays: the kernel statistics
+            # of the roofline come from eager iterations of the same step, right after (one
+            # process: only with --full; the data-parallel path runs them as it always has)
+            nprof = max(3, min(steps, 10))
+            K.profile_begin(capacity=400 * nprof + 64)
+            with torch.cuda.stream(side):
+                for i in range(nprof):
+                    t.iteration(it + i)
+                t.flush()
+            torch.cuda.current_stream().wait_stream(side)
+            barrier()
+            prof = K.profile_end()
+            prof["steps"] = nprof
         del graph
     else:
         graph_segments = 0
@@ -292,6 +337,7 @@ def _run_workload(name, steps, warmup, world, args, K, dp_path=False, host_rng=F
         elapsed = time.perf_counter() - t0
         prof = K.profile_end()
         prof["steps"] = steps
+        outputs = step_outputs(t) if dump else None
     if world > 1:
         e = torch.tensor([elapsed], device="cuda")
         torch.distributed.all_reduce(e, op=torch.distributed.ReduceOp.MAX)
@@ -300,7 +346,7 @@ def _run_workload(name, steps, warmup, world, args, K, dp_path=False, host_rng=F
            "arch": ARCH.get(name, 0), "batch_D": t.batch_D, "elapsed": elapsed, "steps": steps, "mode": mode,
            "segments": graph_segments,
            "value": bpg * world * steps / elapsed, "ms_per_step": 1000.0 * elapsed / steps,
-           "flops_iter": flops_iter, "prof": prof, "graph": use_graph}
+           "flops_iter": flops_iter, "prof": prof, "graph": use_graph, "outputs": outputs}
     del t, images
     torch.cuda.empty_cache()
     return res
@@ -446,8 +492,17 @@ def main():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--workload", default=DEFAULT_WORKLOAD, choices=sorted(WORKLOADS))
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline figure: on one GPU the graph mode's roofline "
+                         "(eager iterations after the timed replays), the extra workloads, the "
+                         "bf16x6 re-run, dp_path_n1, host_draws_n1, hbm_kernels and the CPU baselines "
+                         "(each with its --no-* switch)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step left with its caller (losses, D outputs, the updated "
+                         "nets; large tensors as a fixed seeded sample) as DIR/<name>.npy (rank 0)")
     ap.add_argument("--extra", default=",".join(EXTRA_WORKLOADS),
-                    help="comma-separated workloads also measured on one GPU (extra_workloads); '' = none")
+                    help="with --full: comma-separated workloads also measured on one GPU (extra_workloads); "
+                         "'' = none")
     ap.add_argument("--batch-d", default="auto", choices=("auto", "on", "off"),
                     help="D(x), D(x_fake) as one batched pass (auto = on, also under DP; off = the "
                          "reference's separate D(x) / D(x_fake) calls)")
@@ -509,12 +564,15 @@ def main():
     pg = ({"backend": str(torch.distributed.get_backend()), "world_size": torch.distributed.get_world_size(),
            "launcher": os.environ.get("RGAN_BENCH_LAUNCHER", "external (torch.distributed.run)")}
           if distributed else None)
-    res = run_workload(args.workload, args.steps, args.warmup, world, args, K)
+    res = run_workload(args.workload, args.steps, args.warmup, world, args, K,
+                       dump=args.dump_outputs is not None and rank == 0)
+    if res["outputs"] is not None:
+        dump_outputs(args.dump_outputs, res["outputs"])
     emu_res = None
-    if world == 1 and not args.no_emu_extra:
+    if world == 1 and args.full and not args.no_emu_extra:
         emu_res = run_workload(args.workload, args.steps, min(args.warmup, 5), world, args, K, emu=True)
     extras, dp_paths, host_draws = {}, {}, {}
-    if world == 1:
+    if world == 1 and args.full:
         for name in [w for w in args.extra.split(",") if w and w != args.workload]:
             r = run_workload(name, args.steps, min(args.warmup, 5), world, args, K)
             extras[name] = {"workload": describe(r), "value": r["value"], "unit": "images/s",
@@ -554,8 +612,12 @@ def main():
                    "forced_dp": bool(args.force_dp), "process_group": pg},
         "step_mfma_util": res["flops_iter"] * args.steps / res["elapsed"] / (world * FP32_MFMA_PEAK),
         "conv_tflop_per_step": res["flops_iter"] / 1e12,
-        "roofline": roofline_of(res, args.workload),
     }
+    if res["prof"] is not None:
+        out["roofline"] = roofline_of(res, args.workload)
+    if args.dump_outputs is not None:
+        out["outputs"] = {"dir": args.dump_outputs, "arrays": len(res["outputs"]),
+                          "bytes": sum(a.nbytes for a in res["outputs"].values())}
     if extras:
         out["extra_workloads"] = extras
     if dp_paths:
@@ -574,9 +636,9 @@ def main():
                           "pieces, 6 bf16 MFMA products accumulated in fp32 (weight gradients: fp32 MFMA)",
             "roofline": roofline_of(emu_res, args.workload),
             "parity": emu_parity_evidence()}
-    if world == 1 and not args.no_hbm:
+    if world == 1 and args.full and not args.no_hbm:
         out["hbm_kernels"] = hbm_kernels(args.workload, K)
-    if world == 1 and not args.no_cpu_baseline:
+    if world == 1 and args.full and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(res["loss_D"], res["size"], res["bpg"], res["h"], res["spectral"],
                                            args.cpu_seconds, arch=res["arch"])
         out["cpu_baseline"]["restatement_check"] = restatement_check()

@@ -28,8 +28,39 @@ def _env():
     return env
 
 
+def test_bench_plain_run_is_lean_and_dumps_outputs(tmp_path):
+    """A plain run measures the headline figure only; --dump-outputs writes the last timed
+    step's results (losses, D outputs, the updated nets) as float .npy files."""
+    import numpy
+    out = tmp_path / "dump"
+    r = subprocess.run([sys.executable, "bench.py", "--gpus", "1", "--workload", "C1", "--steps", "3", "--warmup", "1",
+                        "--dump-outputs", str(out)], cwd=ROOT, env=_env(), capture_output=True, text=True,
+                       timeout=240)
+    assert r.returncode == 0, r.stderr[-3000:]
+    d = _line(r.stdout)
+    assert (KEYS - {"roofline"}) <= set(d)
+    assert d["n_gpus"] == 1 and d["steps"] == 3 and d["value"] > 0 and d["dtype"] == "fp32"
+    assert d["unit"] == "images/s" and d["higher_is_better"] is True
+    assert d["ms_per_step"] == pytest.approx(1000.0 * 32 / d["value"], rel=1e-9)
+    for key in ("roofline", "extra_workloads", "dp_path_n1", "host_draws_n1", "fp32_emulated_bf16x6", "hbm_kernels",
+                "cpu_baseline"):
+        assert key not in d, key
+    files = sorted(p.name for p in out.iterdir())
+    assert {"errD.npy", "errG.npy", "D_step.y_pred.npy", "D_step.y_pred_fake.npy", "G_step.y_pred_fake.npy",
+            "G_step.y_pred.npy"} <= set(files)
+    assert any(f.startswith("G.") for f in files) and any(f.startswith("D.") for f in files)
+    total = 0
+    for f in files:
+        a = numpy.load(out / f)
+        assert a.dtype in (numpy.float32, numpy.float64), (f, a.dtype)
+        assert numpy.isfinite(a).all(), f
+        total += a.nbytes
+    assert 0 < total <= 64 * 2 ** 20 and d["outputs"]["bytes"] == total
+    assert numpy.load(out / "D_step.y_pred.npy").shape[0] == 32
+
+
 def test_bench_one_gpu_line():
-    r = subprocess.run([sys.executable, "bench.py", "--workload", "C1", "--extra=", "--no-emu-extra",
+    r = subprocess.run([sys.executable, "bench.py", "--full", "--workload", "C1", "--extra=", "--no-emu-extra",
                         "--no-cpu-baseline", "--steps", "3", "--warmup", "1"], cwd=ROOT, env=_env(),
                        capture_output=True, text=True, timeout=240)
     assert r.returncode == 0, r.stderr[-3000:]

@@ -67,8 +67,8 @@ def _build():
     with ThreadPoolExecutor(max_workers=min(8, max(1, len(jobs)))) as ex:
         list(ex.map(run, jobs))
     exe = os.path.join(BUILD, "abi_fuzz")
-    subprocess.run([HIPCC, "--offload-arch=gfx950", "-fsanitize=address", "-fsanitize=undefined", "-o", exe, hobj,
-                    *objs], check=True, capture_output=True)
+    # the sanitizer runtimes are linked into the host program only (-Xarch_host), like the objects
+    subprocess.run([HIPCC, "--offload-arch=gfx950", *SAN, "-o", exe, hobj, *objs], check=True, capture_output=True)
     return exe
 
 

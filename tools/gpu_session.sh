@@ -1,7 +1,7 @@
 #!/bin/bash
 # One GPU-box session.  usage: tools/gpu_session.sh TAG [step ...]
 #   tests           pytest -m gpu (parity audit JSON under gpurun_out/TAG/parity)
-#   bench[=W]       bench.py default line (or workload W, no extras) -> TAG/bench[_W].json
+#   bench[=W]       bench.py --full line (or workload W, no extra workloads) -> TAG/bench[_W].json
 #   prof[=W]        rocprofv3 --kernel-trace --stats of a short eager bench run -> TAG/prof[_W]/summary.txt
 #   pmc[=W]         FETCH_SIZE / WRITE_SIZE passes -> TAG/pmc[_W]/traffic.json
 #   convs[=W]       tools/conv_breakdown.py: per-call GEMM time by layer shape -> TAG/convs[_W].txt
@@ -27,7 +27,7 @@ for s in $steps; do
         --timeout-method thread -p no:cacheprovider --durations=40 > "$out/pytest.log" 2>&1
       rc=$?; echo "tests rc=$rc"; grep -A45 "slowest" "$out/pytest.log" | tail -46; tail -2 "$out/pytest.log"; stop $rc tests ;;
     bench*)
-      timeout -k 10 500 python -u bench.py $wl > "$out/bench$sfx.json" 2> "$out/bench$sfx.err"
+      timeout -k 10 500 python -u bench.py --full $wl > "$out/bench$sfx.json" 2> "$out/bench$sfx.err"
       rc=$?; echo "bench$sfx rc=$rc"; stop $rc bench ;;
     prof*)
       timeout -k 10 450 tools/profile_bench.sh "$out/prof$sfx" --steps 10 --warmup 3 --no-cpu-baseline --no-emu-extra --no-dp-path --no-host-draws --no-hbm --graph off \
