@@ -270,9 +270,9 @@ int rgan_bn_backward_parts(const float* g, const float* y, long long P, int C, i
 /* The staged backward's sums and apply in one call (ABI 4; one process or per-shard BN): writes
  * sums[2][C] = (sum g, sum g (y - mean)), g = da * act' (the WGAN-GP engine keeps them for the
  * double backward), dy = BN-backward(g) + add (add nullable), dgamma / dbeta written or, with
- * accumulate_affine, added into (nullable).  Dense NHWC da, y, dy, add.  P <= 2048 rows (C % 16
- * == 0): one launch; otherwise rgan_bn_backward_sums + rgan_bn_backward_apply_ex.  partial:
- * rgan_bn_partial_bytes(P, C). */
+ * accumulate_affine, added into (nullable).  Dense NHWC da, y, dy, add; add may be dy itself
+ * (added in place).  P <= 2048 rows and C >= 1024 (C % 16 == 0): one launch; otherwise
+ * rgan_bn_backward_sums + rgan_bn_backward_apply_ex.  partial: rgan_bn_partial_bytes(P, C). */
 int rgan_bn_backward_sums_apply(const float* da, const float* y, long long P, int C, const float* stats,
                                 const float* gamma, const float* beta, int act, float act_alpha, const float* add,
                                 float* dy, float* dgamma, float* dbeta, int accumulate_affine, double* sums,

@@ -722,6 +722,7 @@ __global__ __launch_bounds__(256) void bn_bwd_partial(const float* __restrict__ 
 // dy = al*(g - sum_g/Pg - (y-mean)*invstd^2*sum_gx/Pg); dgamma = invstd*sum_gx, dbeta = sum_g
 // NSEG 2: rows [0, seg_rows) with stats / sums row 0, the rest with row 1 (the batched
 // pass's two calls); the affine gradients are the segments' sum (segment order)
+// add may be dy itself (the WGAN-GP engine adds in place): neither is __restrict__
 template <int Q, int NSEG = 1>
 __global__ __launch_bounds__(256) void bn_bwd_apply(const float* __restrict__ da, long long dsp, long long dsc,
                                                     const float* __restrict__ y, long long P, int C, long long sp,
@@ -729,9 +730,9 @@ __global__ __launch_bounds__(256) void bn_bwd_apply(const float* __restrict__ da
                                                     const float* __restrict__ gamma,
                                                     const float* __restrict__ beta, int act, float alpha,
                                                     const double* __restrict__ sums, double inv_pg,
-                                                    float* __restrict__ dy, long long ysp, long long ysc,
+                                                    float* dy, long long ysp, long long ysc,
                                                     float* dgamma, float* dbeta, int tpr,
-                                                    const float* __restrict__ add, int accum_affine,
+                                                    const float* add, int accum_affine,
                                                     long long seg_rows = 0) {
   const int tid = threadIdx.x, lc = tid % tpr, rl = tid / tpr, rp = blockDim.x / tpr;
   const int c0 = (blockIdx.x * tpr + lc) * Q;
@@ -819,6 +820,7 @@ __global__ __launch_bounds__(256) void bn_bwd_apply(const float* __restrict__ da
 // rows per lane one dependent round trip at a time, 24-28 us per call at C = 128-256 in the
 // WGAN-GP engine; every row of a <= 2048-row single call now stays in registers, 128 VGPRs of
 // the 256 two waves per SIMD allow)
+// add may be dy itself, as in bn_bwd_apply: neither is __restrict__
 constexpr int BNS_LANES = 128, BNS_CH = 16, BNS_THREADS = 512;
 constexpr long long BNS_MAX_ROWS = 2048;  // rows per segment
 template <int NSEG>
@@ -826,8 +828,8 @@ __global__ __launch_bounds__(BNS_THREADS) void bn_bwd_small(const float* __restr
                                                             long long Ps, int C, const float* __restrict__ stats,
                                                             const float* __restrict__ gamma,
                                                             const float* __restrict__ beta, int act, float alpha,
-                                                            float* __restrict__ dy, float* dgamma, float* dbeta,
-                                                            const float* __restrict__ add = nullptr,
+                                                            float* dy, float* dgamma, float* dbeta,
+                                                            const float* add = nullptr,
                                                             int accum_affine = 0, double* sums_out = nullptr) {
   constexpr int RC = 16 / NSEG;  // rows per segment cached in registers
   constexpr int NW = BNS_THREADS / 64;

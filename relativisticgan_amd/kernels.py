@@ -617,9 +617,9 @@ def bn_backward_apply(da, y, stats, gamma, beta, act, alpha, sums, P_global, nee
 def bn_backward_sums_apply(da, y, stats, gamma, beta, act, alpha, add=None, out=None, dgamma=None, dbeta=None,
                            accumulate_affine=False):
     """(sums double[2C], dy) of act(BN(y))'s backward in one call (rgan_bn_backward_sums_apply:
-    one launch for <= 2048 rows): sums as bn_backward_sums returns them, dy = BN-backward(da *
-    act') + add; dgamma / dbeta (given buffers) written or, with accumulate_affine, added into.
-    Dense NHWC da / y / out / add."""
+    one launch for <= 2048 rows, C % 16 == 0 and C >= 1024): sums as bn_backward_sums returns
+    them, dy = BN-backward(da * act') + add; dgamma / dbeta (given buffers) written or, with
+    accumulate_affine, added into.  Dense NHWC da / y / out / add; add may be out itself."""
     if not is_nhwc(da):
         da = da.contiguous(memory_format=torch.channels_last)
     P, C, _, _ = _pc(y)

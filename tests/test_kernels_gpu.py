@@ -1146,36 +1146,99 @@ def test_bn_segment_apply_one_call(K, B, cin, H, cout, tr, nseg):
     assert same(rm1, rm2) and same(rv1, rv2) and int(n2.item()) == nseg
 
 
-@pytest.mark.parametrize("C,B,H", [(256, 32, 4), (128, 32, 8), (64, 32, 16), (64, 32, 32), (36, 8, 8)])
+def _bn_off_kink(y, gamma, beta, eps=1e-5):
+    """y (fp32, CPU) with every |z| >= 1e-3, z = gamma * xhat + beta in fp64 with y's own batch
+    statistics: elements nearer move 0.05 in y, away from zero (at most three rounds, then
+    asserted), so fp32 rounding of z (~1e-5) cannot flip a branch of ReLU' / LeakyReLU'.
+    -> (y fp32, its fp64 batch mean, 1 / sqrt(var + eps))."""
+    g64, b64 = gamma.double()[None, :, None, None], beta.double()[None, :, None, None]
+
+    def pre(y64):
+        mean = y64.mean((0, 2, 3))
+        inv = 1.0 / torch.sqrt(y64.var((0, 2, 3), unbiased=False) + eps)
+        return g64 * (y64 - mean[None, :, None, None]) * inv[None, :, None, None] + b64, mean, inv
+
+    y64 = y.double()
+    for _ in range(3):
+        z, _, _ = pre(y64)
+        near = z.abs() < 1e-3
+        if not bool(near.any()):
+            break
+        away = torch.where(z < 0, -1.0, 1.0) * torch.sign(g64)
+        y64 = torch.where(near, y64 + 0.05 * away, y64).float().double()
+    z, mean, inv = pre(y64)
+    assert z.abs().min().item() >= 1e-3
+    return y64.float(), mean, inv
+
+
+# C <= 256: the two-call path at any row count (too few channel groups for one launch);
+# C >= 1024: bn_bwd_small in one launch up to 2048 rows (512; 128; 147 = ragged over the
+# 128 row lanes; exactly 2048) and the two-call path just past them (2112)
+@pytest.mark.parametrize("C,B,H", [(256, 32, 4), (128, 32, 8), (64, 32, 16), (64, 32, 32), (36, 8, 8),
+                                   (1024, 32, 4), (2048, 8, 4), (1024, 3, 7), (1024, 32, 8), (1024, 33, 8)])
 def test_bn_backward_sums_apply_one_call(K, C, B, H):
     """rgan_bn_backward_sums_apply (the WGAN-GP engine's BatchNorm backward: sums kept, + add,
     affine gradients accumulated) == rgan_bn_backward_sums + rgan_bn_backward_apply_ex: within
-    1e-6 on the one-launch small-layer kernel (<= 2048 rows, C % 16 == 0: its double sums
-    associate differently), bitwise on the two-call path."""
+    1e-6 on the one-launch small-layer kernel (<= 2048 rows, C % 16 == 0, C >= 1024: its double
+    sums associate differently), bitwise on the two-call path; add both aliased to out (as
+    the GP engine runs it) and separate.  The C >= 1024 cases also against fp64 autograd with
+    y's true batch statistics (rel L2 < 2e-5: sums, dy, the accumulated dgamma / dbeta)."""
     torch.manual_seed(31)
     P = B * H * H
-    small = P <= 2048 and C % 16 == 0
+    small = P <= 2048 and C % 16 == 0 and C // 16 >= 64  # rgan_bn_backward_sums_apply's rule
     same = (lambda a, b: torch.allclose(a, b, rtol=1e-6, atol=1e-6)) if small else torch.equal
+    fn = {"relu": F.relu, "lrelu": lambda t: F.leaky_relu(t, 0.2), "tanh": torch.tanh}
     for act, with_add in (("lrelu", True), ("relu", False), ("tanh", True)):
-        y = _nhwc(torch.randn(B, C, H, H, device=DEV))
+        gamma, beta = torch.rand(C, device=DEV) + 0.5, torch.randn(C, device=DEV)
+        if C >= 1024:
+            y_c, mean, inv = _bn_off_kink(torch.randn(B, C, H, H), gamma.cpu(), beta.cpu())
+            y = _nhwc(y_c.to(DEV))
+            stats = torch.cat([mean, inv]).float().to(DEV)
+        else:
+            y = _nhwc(torch.randn(B, C, H, H, device=DEV))
+            stats = torch.cat([torch.randn(C, device=DEV), torch.rand(C, device=DEV) + 0.5])
         da = _nhwc(torch.randn(B, C, H, H, device=DEV))
         add = _nhwc(torch.randn(B, C, H, H, device=DEV)) if with_add else None
-        stats = torch.cat([torch.randn(C, device=DEV), torch.rand(C, device=DEV) + 0.5])
-        gamma, beta = torch.rand(C, device=DEV) + 0.5, torch.randn(C, device=DEV)
         g0, b0 = torch.randn(C, device=DEV), torch.randn(C, device=DEV)
         dg1, db1 = g0.clone(), b0.clone()
         sums1, da_c = K.bn_backward_sums(da, y, stats, gamma, beta, act, 0.2)
         dy1 = K.bn_backward_apply_ex(da_c, y, stats, gamma, beta, act, 0.2, sums1, P,
                                      add=add.clone() if add is not None else None, dgamma=dg1, dbeta=db1,
                                      accumulate_affine=True)
-        dg2, db2 = g0.clone(), b0.clone()
-        out = add.clone() if add is not None else None  # in place over the addend, as the GP engine runs it
-        sums2, dy2 = K.bn_backward_sums_apply(da, y, stats, gamma, beta, act, 0.2, add=out, out=out, dgamma=dg2,
-                                              dbeta=db2, accumulate_affine=True)
-        assert same(sums1, sums2) and same(dy1, dy2) and same(dg1, dg2) and same(db1, db2), (act, with_add)
+        runs = []
+        for aliased in ((True, False) if with_add else (False,)):
+            dg2, db2 = g0.clone(), b0.clone()
+            # in place over the addend, as the GP engine runs it / a separate addend
+            out = add.clone() if aliased else torch.full_like(y, float("nan"))
+            sums2, dy2 = K.bn_backward_sums_apply(da, y, stats, gamma, beta, act, 0.2, add=out if aliased else add,
+                                                  out=out, dgamma=dg2, dbeta=db2, accumulate_affine=True)
+            assert same(sums1, sums2) and same(dy1, dy2) and same(dg1, dg2) and same(db1, db2), \
+                (act, with_add, aliased)
+            runs.append((sums2, dy2, dg2, db2))
+        if C < 1024:
+            continue
+        y64 = y.double().cpu().requires_grad_(True)
+        g64, b64 = gamma.double().cpu().requires_grad_(True), beta.double().cpu().requires_grad_(True)
+        z = F.batch_norm(y64, None, None, g64, b64, training=True, momentum=0.0, eps=1e-5)
+        da64 = da.double().cpu()
+        (gz,) = torch.autograd.grad(fn[act](z), z, da64, retain_graph=True)  # g = da * act'(z)
+        dy64, dg64, db64 = torch.autograd.grad(fn[act](z), [y64, g64, b64], da64)
+        if add is not None:
+            dy64 = dy64 + add.double().cpu()
+        sums64 = torch.stack([gz.sum((0, 2, 3)), (gz * (y64.detach() - mean[None, :, None, None])).sum((0, 2, 3))])
+        for sums2, dy2, dg2, db2 in runs:
+            errs = dict(sum_g=_rel(sums2.view(2, C)[0], sums64[0]), sum_gx=_rel(sums2.view(2, C)[1], sums64[1]),
+                        dy=_rel(dy2, dy64), dgamma=_rel(dg2.double() - g0.double(), dg64),
+                        dbeta=_rel(db2.double() - b0.double(), db64))
+            print(f"[bn_sums_apply] C={C} P={P} {act} " + " ".join(f"{k} {v:.3e}" for k, v in errs.items()))
+            assert max(errs.values()) < 2e-5, (act, errs)
 
 
-@pytest.mark.parametrize("C,B,H", [(64, 8, 32), (64, 8, 16), (1024, 64, 4), (4096, 64, 4), (64, 16, 16), (36, 8, 8)])
+# the last three: ragged rows in bn_bwd_small -- 147 and 405 rows per segment (no multiple of
+# its 128 row lanes), and 1083, whose re-read tail past the 8 x 128 rows the two-segment
+# kernel keeps in registers is ragged
+@pytest.mark.parametrize("C,B,H", [(64, 8, 32), (64, 8, 16), (1024, 64, 4), (4096, 64, 4), (64, 16, 16), (36, 8, 8),
+                                   (16, 6, 7), (48, 10, 9), (64, 6, 19)])
 def test_bn_backward_two_segments(K, C, B, H):
     """rgan_bn_backward_segments (both calls of the batched pass at once) == the per-call
     backward sums + apply: dy and the summed affine gradients -- bitwise for the three-launch
