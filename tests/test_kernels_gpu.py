@@ -121,6 +121,65 @@ def test_small_gemm_tiles(K, case):
     assert _rel(dw, w64.grad) < 2e-6
 
 
+# family: (op, (B, cin, cout, H, k, s, p, transposed), x layout, the name the launch profiler reports).
+# The shapes are the smallest that meet the planners' conditions (conv_gemm.hip):
+#   plan_narrow_t     k4 s2 p1 ConvT, <= 4 outputs, NHWC input with C % 4 == 0
+#   plan_narrow_in    k4 Conv, <= 4 inputs; conv_img_in when also s2 p1, cout % 128 == 0, NHWC output,
+#                     wout == 16 (or % 32 == 0) and W-contiguous input rows (NCHW x, W % 4 == 0);
+#                     cout = 8 (neither % 128 nor % 32) stays on conv_narrow_in_mfma
+#   plan_dense1       Conv(C, 1, k, 1, 0) over exactly a k x k map
+#   plan_narrow3_out  k3 s1 Conv, <= 4 outputs, NHWC input, C a power of two in [4, 256]
+#   plan_wgrad3_narrow  the weight gradient of a k3 s1 p1 Conv with <= 4 outputs, cin % 4 == 0
+LAUNCH_NAMES = {
+    "convt2_narrow_mfma": ("fwd", (2, 16, 3, 4, 4, 2, 1, True), "nhwc",
+                           "void rgan::convt2_narrow_mfma<NC>(rgan::NarrowArgs)"),
+    "conv_img_in": ("fwd", (2, 3, 128, 32, 4, 2, 1, False), "nchw",
+                    "void rgan::conv_img_in<CI, WT, ACT>(rgan::NarrowArgs)"),
+    "conv_narrow_in_mfma": ("fwd", (2, 3, 8, 32, 4, 2, 1, False), "nchw",
+                            "void rgan::conv_narrow_in_mfma<CI>(rgan::NarrowArgs)"),
+    "dense1_fwd": ("fwd", (2, 16, 1, 4, 4, 1, 0, False), "nhwc", "void rgan::dense1_fwd<VEC>(rgan::DenseArgs)"),
+    "dense1_dgrad": ("dgrad", (2, 16, 1, 4, 4, 1, 0, False), "nhwc",
+                     "void rgan::dense1_dgrad<VEC>(rgan::DenseArgs, rgan::FastDiv)"),
+    "dense1_wgrad": ("wgrad", (2, 16, 1, 4, 4, 1, 0, False), "nhwc", "rgan::dense1_wgrad(rgan::DenseArgs)"),
+    "conv3_narrow_out": ("fwd", (2, 16, 3, 8, 3, 1, 1, False), "nhwc",
+                         "void rgan::conv3_narrow_out<NC>(rgan::NarrowArgs, int)"),
+    "wgrad3_narrow": ("wgrad", (2, 16, 3, 8, 3, 1, 1, False), "nhwc",
+                      "void rgan::wgrad3_narrow<NC>(rgan::NarrowArgs, int, int)"),
+}
+
+
+@pytest.mark.parametrize("family", sorted(LAUNCH_NAMES))
+def test_launch_profiler_names(K, family):
+    """The launch profiler reports a narrow / dense launch under its own kernel's name (bench.py
+    and profiles/*_pmc_traffic.json key on these strings): one call, one kernel, that name --
+    and the result vs torch fp64.  (The gemm_kernel tiles and the bf16x6 names:
+    test_small_gemm_tiles, test_conv_bf16x6_emulation.)"""
+    op, (B, cin, cout, H, k, s, p, tr), layout, name = LAUNCH_NAMES[family]
+    g = K.ConvGeom(k, s, p, tr)
+    torch.manual_seed(5)
+    x = torch.randn(B, cin, H, H, device=DEV)
+    if layout == "nhwc":
+        x = _nhwc(x)
+    w = torch.randn((cin, cout, k, k) if tr else (cout, cin, k, k), device=DEV) * 0.1
+    x64 = x.double().cpu().requires_grad_(True)
+    w64 = w.double().cpu().requires_grad_(True)
+    out64 = (F.conv_transpose2d if tr else F.conv2d)(x64, w64, stride=s, padding=p)
+    dy = _nhwc(torch.randn(out64.shape, device=DEV))
+    out64.backward(dy.double().cpu())
+    K.profile_begin(64)
+    if op == "fwd":
+        got, ref = K.conv_fwd(x, w, g), out64.detach()
+    elif op == "dgrad":
+        got, ref = K.conv_dgrad(dy, w, g, x.shape), x64.grad
+    else:
+        got, ref = K.conv_wgrad(x, dy, g, tuple(w.shape))[0], w64.grad
+    prof = K.profile_end()
+    assert [kk["name"] for kk in prof["kernels"]] == [name], prof
+    assert prof["launches"] == 1 and prof["kernels"][0]["launches"] == 1, prof
+    assert got.shape == ref.shape
+    assert _rel(got, ref) < 2e-6
+
+
 @pytest.mark.parametrize("case", [(2, 16, 8, 4), (3, 8, 3, 8), (2, 32, 64, 8), (2, 5, 7, 6), (2, 64, 32, 16)])
 @pytest.mark.parametrize("cached", [False, True])
 def test_nn_conv_upsample_fold(K, case, cached):
