@@ -27,7 +27,8 @@ extern "C" {
 
 /* ABI revision.  2: rgan_adam_packed takes step = device float[2] (step[1] is the
  * call's uint32 arrival ticket, zero before the first call); revision 1 took float[1].
- * 3: adds rgan_conv_wgrad_rows.  4: adds rgan_bn_segment_apply and rgan_bn_backward_sums_apply. */
+ * 3: adds rgan_conv_wgrad_rows.  4: adds rgan_bn_segment_apply and rgan_bn_backward_sums_apply.
+ * rgan_diffaug_workspace and rgan_diffaug are additive within revision 4 (nothing else changed). */
 #define RGAN_ABI_VERSION 4
 
 /* Activation codes fused into epilogues (GLI:345,370,388,417,437,450; SELU GLI:338). */
@@ -461,6 +462,31 @@ int rgan_lr_decay(double* hyper, double gamma, void* stream);
  * GLI:176-178, 581-583, on a dataset resident in HBM). */
 int rgan_gather_images(const float* images, const long long* idx, int batch, long long per,
                        float* out, void* stream);
+
+/* ---- differentiable augmentation of D's inputs (--rgan_diffaug; no reference counterpart) ----
+ * (additive within ABI revision 4: no existing entry point changed)
+ * One random colour / translation / cutout transform per sample, for every image D sees, and
+ * its adjoint for the gradient that flows back to G.  x, y: [batch][channels][h][w] contiguous;
+ * u: [batch][8] uniforms in [0, 1), columns 0..6 used (7 reserved).  policy: bit 1 colour,
+ * bit 2 translation, bit 4 cutout; a disabled part takes its identity value.
+ *   colour:      beta = u0 - 1/2, sat = 2 u1, con = u2 + 1/2 (identity 0, 1, 1);
+ *                col(x)[c,i,j] = con (sat (x[c,i,j] - m_ij) + m_ij - mu) + mu + beta,
+ *                m_ij = mean_c x[:,i,j], mu = mean_{c,i,j} x
+ *   translation: R = floor(h/8 + 1/2), tx = min(floor(u3 (2R + 1)), 2R) - R; ty from u4 and w;
+ *                sources outside the image read 0
+ *   cutout:      K = floor(h/2 + 1/2), o = min(floor(u5 (h + 1 - K mod 2)), h - K mod 2), rows
+ *                [o - floor(K/2), o - floor(K/2) + K - 1] of the output are 0; columns from u6, w
+ *   adjoint = 0: y[c,i,j] = col(x)[c,i+tx,j+ty], or 0 inside the box / for a source outside
+ *   adjoint != 0 (x is dy, y is dx): g = dy moved back (0 where nothing arrives), then
+ *                dx = con (sat g + (1 - sat) mean_c g) + (1 - con) mean_{c,i,j} g
+ * The sample mean is a two-stage sum through ws (rgan_diffaug_workspace floats, only written
+ * with the colour bit) added in a fixed order: no atomics, two calls give the same bits.
+ * Without the colour bit every output is a copied input value or 0.  y must not alias x.
+ * 16-byte loads and stores when w % 4 == 0 and x, y are 16-byte aligned; any w, alignment and
+ * channel count otherwise.  batch <= 65535, channels*h*w < 2^31. */
+size_t rgan_diffaug_workspace(int batch, int channels, int h, int w);
+int rgan_diffaug(const float* x, const float* u, int batch, int channels, int h, int w, int policy,
+                 int adjoint, float* ws, float* y, void* stream);
 
 /* ---- live launch timing (bench.py roofline) ----
  * rgan_profile_begin(capacity): bracket each subsequent conv GEMM launch with HIP events

@@ -5,7 +5,8 @@ Plus this build's own switches (prefixed ``--rgan_``), which the reference lacks
 order, bit-compatible inputs; ``device``: draw on the GPU, for throughput runs) and
 ``--rgan_sync_bn`` (BatchNorm statistics under data parallelism: default off = the
 reference's DataParallel, each rank normalises with its own shard; on = SyncBN over the
-global batch), ``--rgan_pac 2`` (the PacGAN-2 script,
+global batch), ``--rgan_diffaug`` (differentiable augmentation of D's inputs, off by
+default; relativisticgan_amd/augment.py), ``--rgan_pac 2`` (the PacGAN-2 script,
 code/GAN_losses_iter_PAC.py, which shares this CLI) and ``--rgan_script`` (the defaults of
 GAN_losses_iter / GAN_losses_iter_art / GAN_losses_iter_PAC).
 """
@@ -70,6 +71,10 @@ def make_parser(script="GAN_losses_iter"):
                    choices=(1, 2),
                    help="2 = PacGAN-2, the reference's code/GAN_losses_iter_PAC.py (D sees 2 samples packed "
                         "channel-wise)")
+    p.add_argument("--rgan_diffaug", default="",
+                   help="differentiable augmentation of every image D sees, reals and fakes, with G's gradient "
+                        "flowing back through it: a comma-separated subset of color,translation,cutout "
+                        "(default '': off; not with --rgan_pac 2)")
     p.add_argument("--rgan_perf_log", type="bool", default=True,
                    help="after each reference log line, a line with img/s and MFMA%% of the training "
                         "iterations since the previous one (sample PNGs, checkpoints and extra images excluded)")
@@ -82,7 +87,14 @@ def parse(argv=None):
     pre = argparse.ArgumentParser(add_help=False)
     pre.add_argument("--rgan_script", choices=SCRIPTS, default="GAN_losses_iter")
     script = pre.parse_known_args(argv)[0].rgan_script
-    return make_parser(script).parse_args(argv)
+    parser = make_parser(script)
+    ns = parser.parse_args(argv)
+    try:
+        from .augment import validate
+        validate(ns.rgan_diffaug, ns.pac)
+    except ValueError as e:
+        parser.error(str(e))  # exits with the message
+    return ns
 
 
 def make_param(**overrides):

@@ -1081,6 +1081,31 @@ def gather_images(images, idx, out=None):
     return out
 
 
+# ------------------------------------------------------------------ differentiable augmentation
+def diffaug(x, u, policy, adjoint=False, out=None):
+    """The per-sample colour / translation / cutout transform of include/rgan.h rgan_diffaug
+    (``policy``: bit 1 colour, 2 translation, 4 cutout; ``u``: [B][8] uniforms), or with
+    ``adjoint`` its transpose applied to a gradient.  ``out``: a contiguous buffer other than
+    ``x`` (e.g. half of a batched D input)."""
+    L.require_cuda(x, u, out)
+    if x.dim() != 4 or x.dtype != torch.float32 or u.dtype != torch.float32:
+        raise L.RganError("diffaug: x must be a float32 [B][C][H][W] tensor and u float32")
+    B, C, H, W = x.shape
+    if tuple(u.shape) != (B, 8):
+        raise L.RganError(f"diffaug: u must be [{B}][8] (one row of uniforms per sample), got {tuple(u.shape)}")
+    x = x.contiguous()
+    u = u.contiguous()
+    if out is None:
+        out = torch.empty_like(x)
+    elif not out.is_contiguous() or out.shape != x.shape or out.dtype != torch.float32:
+        raise L.RganError("diffaug: out must be contiguous float32 and shaped like x")
+    lib = L.lib()
+    ws = torch.empty(max(int(lib.rgan_diffaug_workspace(B, C, H, W)), 1), dtype=torch.float32, device=x.device)
+    L.check(lib.rgan_diffaug(L.ptr(x), L.ptr(u), B, C, H, W, int(policy), int(bool(adjoint)), L.ptr(ws), L.ptr(out),
+                             L.stream()), "rgan_diffaug")
+    return out
+
+
 # ------------------------------------------------------------------ GEMM arithmetic
 def set_gemm_emulation(on):
     """Run the FAST 128x128 forward / data-gradient conv GEMMs as fp32 emulated on the bf16 MFMA

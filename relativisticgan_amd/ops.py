@@ -21,6 +21,8 @@ dispatcher-level tracers see the MI355X kernels as graph nodes (not opaque Pytho
   rgan::loss_head_grad
   rgan::gp_penalty       lam * mean((||g_b|| - 1)^2)                               GLI:646-658
   rgan::gp_penalty_backward
+  rgan::diffaug          colour / translation / cutout of D's inputs (--rgan_diffaug; not in the reference)
+  rgan::diffaug_backward its adjoint
   rgan::adam_            torch.optim.Adam's single-tensor step (mutating)          GLI:659,712
 
 Differentiability: every op above has a first-order formula; conv2d / conv2d_dgrad /
@@ -451,6 +453,48 @@ gp_penalty_backward.register_autograd(_no_double("gp_penalty_backward"),
                                       setup_context=lambda ctx, inputs, output: None)
 
 
+# ------------------------------------------------------------------ differentiable augmentation
+@torch.library.custom_op("rgan::diffaug", mutates_args=(), device_types=_DEV)
+def diffaug(x: torch.Tensor, u: torch.Tensor, policy: int) -> torch.Tensor:
+    """The per-sample colour / translation / cutout transform of D's inputs (policy bits 1 / 2 /
+    4; u [B][8] uniforms; include/rgan.h rgan_diffaug)."""
+    return K.diffaug(x, u, policy)
+
+
+@diffaug.register_fake
+def _(x, u, policy):
+    return torch.empty(x.shape, dtype=torch.float32, device=x.device)
+
+
+def _aug_setup(ctx, inputs, output):
+    x, u, policy = inputs
+    ctx.policy = policy
+    ctx.save_for_backward(u)
+
+
+def _aug_backward(ctx, g):
+    u, = ctx.saved_tensors
+    return torch.ops.rgan.diffaug_backward(g, u, ctx.policy), None, None
+
+
+diffaug.register_autograd(_aug_backward, setup_context=_aug_setup)
+
+
+@torch.library.custom_op("rgan::diffaug_backward", mutates_args=(), device_types=_DEV)
+def diffaug_backward(g: torch.Tensor, u: torch.Tensor, policy: int) -> torch.Tensor:
+    """The transform's adjoint applied to g (rgan_diffaug with adjoint = 1): the transform is
+    affine in x for fixed u, so this is its whole derivative."""
+    return K.diffaug(g, u, policy, adjoint=True)
+
+
+@diffaug_backward.register_fake
+def _(g, u, policy):
+    return torch.empty(g.shape, dtype=torch.float32, device=g.device)
+
+
+diffaug_backward.register_autograd(_no_double("diffaug_backward"), setup_context=lambda ctx, inputs, output: None)
+
+
 # ------------------------------------------------------------------ optimizer
 @torch.library.custom_op("rgan::adam_", mutates_args=("params", "exp_avgs", "exp_avg_sqs", "step"),
                          device_types=_DEV)
@@ -497,4 +541,4 @@ def layer_forward(layer, h, training):
 
 OPS = ("conv2d", "conv2d_dgrad", "conv2d_wgrad", "channel_sum", "act_backward", "batch_norm_stats_",
        "batch_norm_apply", "batch_norm_backward", "spectral_power_", "spectral_scale", "spectral_backward", "loss_head",
-       "loss_head_grad", "gp_penalty", "gp_penalty_backward", "adam_")
+       "loss_head_grad", "gp_penalty", "gp_penalty_backward", "diffaug", "diffaug_backward", "adam_")

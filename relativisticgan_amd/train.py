@@ -18,7 +18,7 @@ import time
 import numpy
 import torch
 
-from . import autograd, dp
+from . import augment, autograd, dp
 from .config import TITLES, parse
 from .kernels import DeviceRNG
 from .losses import gradient_penalty, loss_D, loss_D_cat, loss_D_fake, loss_D_real, loss_G, loss_G_cat, unit_seed
@@ -96,6 +96,8 @@ class Trainer:
         self.dev_rng = (None if self.host_rng else
                         DeviceRNG(p.seed if p.seed is not None else torch.initial_seed(), self.device))
         self.pac = getattr(p, "pac", 1)  # 2: code/GAN_losses_iter_PAC.py
+        # --rgan_diffaug: the kernel's policy mask (0 = off: no call, no draw)
+        self.aug = augment.validate(getattr(p, "rgan_diffaug", ""), self.pac)
         # one batched D pass per D step where the nets allow it (--rgan_batch_D).  Default
         # (auto): on, under data parallelism too.  G's gradient buckets all-reduce while G's
         # own backward runs (GradReducer), so the deferred G step (flush, right before the
@@ -165,6 +167,28 @@ class Trainer:
             return self._shard(torch.empty(shape).uniform_(0, 1)).to(self.device, non_blocking=True)
         return self._shard(self.dev_rng.uniform(shape))
 
+    def _aug_u(self, feed, key, groups):
+        """This rank's [groups*B][8] augmentation uniforms: one draw of groups * batch_size rows
+        for the global batch (group k = rows [k*batch_size, (k+1)*batch_size)), each group
+        sharded like ``_uniform``."""
+        if feed is not None and key in feed:
+            return feed[key]
+        n = self.p.batch_size
+        u = augment.draw(groups * n, self.host_rng, self.dev_rng)
+        if self.world > 1:
+            u = torch.cat([self._shard(u[k * n:(k + 1) * n]) for k in range(groups)])
+        return u.to(self.device, non_blocking=True)
+
+    def _augment_pair(self, a, b, u, raw, out):
+        """T(a), T(b) with u's two row groups, written back to back into ``out``: one call over
+        both when a and b already lie back to back in ``raw``.  a may carry autograd."""
+        B = self.B
+        if (raw is not None and not a.requires_grad and a.data_ptr() == raw.data_ptr()
+                and b.data_ptr() == raw[B:].data_ptr()):
+            augment.apply(raw, u, self.aug, out=out)
+            return out[:B], out[B:]
+        return augment.apply(a, u[:B], self.aug, out=out[:B]), augment.apply(b, u[B:], self.aug, out=out[B:])
+
     def _generate_D(self, z, out=None):
         """The D step's fake batch.  Single samples: G(z) without a graph (GLI copies it into
         x_fake's .data), written into ``out`` when given.  PacGAN: keep G's graph for the G
@@ -213,13 +237,26 @@ class Trainer:
                 # the batched D pass reads it as is (no concatenation)
                 pair = torch.empty((2 * self.B, p.n_colors, p.image_size, p.image_size), dtype=torch.float32,
                                    device=self.device)
-            x = self._real(feed, "x_D", out=pair[:self.B] if pair is not None else None)
+            # --rgan_diffaug: x and G(z) go to a buffer of their own and the transform writes
+            # the pair D reads (same layout); x_raw is the untransformed batch of the record
+            raw = torch.empty_like(pair) if pair is not None and self.aug else pair
+            x = x_raw = self._real(feed, "x_D", out=raw[:self.B] if raw is not None else None)
+            z = u_aug = None
+            if self.aug and not self.batch_D:
+                # the separate passes run D(x) before G(z): draw z now, so the draws come in the
+                # batched path's order (x, z, augmentation) whichever path runs
+                z = self._normal(feed, "z_D", zshape)
+                u_aug = self._aug_u(feed, "aug_D", 2)
+                x = augment.apply(x, u_aug[:self.B], self.aug)
             if self.batch_D:
                 # D(x) and D(x_fake) as one batched pass (per-call BN statistics kept):
                 # the draws keep the reference's order (x, then z); D(x) does not read G
                 z = self._normal(feed, "z_D", zshape)
                 self.flush()
-                x_fake = self._generate_D(z, out=pair[self.B:] if pair is not None else None)
+                x_fake = self._generate_D(z, out=raw[self.B:] if raw is not None else None)
+                if self.aug:
+                    u_aug = self._aug_u(feed, "aug_D", 2)
+                    x, x_fake = self._augment_pair(x, x_fake, u_aug, raw, pair)
                 laid_out = (pair is not None and x.data_ptr() == pair.data_ptr()
                             and x_fake.data_ptr() == pair[self.B:].data_ptr())
                 y_all = D.forward_pair(x, x_fake, cat=pair if laid_out else None)
@@ -235,9 +272,12 @@ class Trainer:
                 y_pred = D(x)
                 err_real = loss_D_real(kind, y_pred)
                 self._backward(err_real)
-                z = self._normal(feed, "z_D", zshape)
+                if z is None:
+                    z = self._normal(feed, "z_D", zshape)
                 self.flush()
                 x_fake = self._generate_D(z)
+                if self.aug:
+                    x_fake = augment.apply(x_fake, u_aug[self.B:], self.aug)
                 y_pred_fake = D(x_fake)
                 err_fake = loss_D_fake(kind, y_pred_fake)
                 if not gp_on:
@@ -246,17 +286,23 @@ class Trainer:
                 errD = err_real.detach() + err_fake.detach()
             else:
                 y_pred = D(x)
-                z = self._normal(feed, "z_D", zshape)
+                if z is None:
+                    z = self._normal(feed, "z_D", zshape)
                 self.flush()
                 x_fake = self._generate_D(z)
+                if self.aug:
+                    x_fake = augment.apply(x_fake, u_aug[self.B:], self.aug)
                 y_pred_fake = D(x_fake)
                 errD = loss_D(kind, y_pred, y_pred_fake)
                 if not gp_on:
                     self._arm(self.redD)
                 self._backward(errD)
-            rec = {"x": x, "z": z, "y_pred": y_pred.detach(), "y_pred_fake": y_pred_fake.detach(),
+            rec = {"x": x_raw, "z": z, "y_pred": y_pred.detach(), "y_pred_fake": y_pred_fake.detach(),
                    "errD": errD.detach()}
+            if self.aug:
+                rec.update(aug=u_aug, x_aug=x, x_fake_aug=x_fake)
             if gp_on:
+                # with augmentation on, x and x_fake are the transformed batches: what D saw
                 u = self._uniform(feed, "u", (p.batch_size, 1, 1, 1))
                 gp = gradient_penalty(D, x, x_fake, u, p.penalty)
                 self._arm(self.redD)
@@ -282,7 +328,7 @@ class Trainer:
                 # output and the gather its images into one buffer, back to back
                 pair_G = torch.empty((2 * self.B, p.n_colors, p.image_size, p.image_size), dtype=torch.float32,
                                      device=self.device)
-                fake = G(z, out=pair_G[:self.B])
+                fake = G(z, out=None if self.aug else pair_G[:self.B])
             elif self.pac == 1:
                 fake = G(z)
             else:
@@ -296,20 +342,34 @@ class Trainer:
             if pair_G is not None:
                 # GLI:674 then GLI:677-682 + 695-707: the draw order (z, then the real batch)
                 # and the BN call order (D(fake), then D(x)) are the reference's
-                x = self._real(feed, "x_G", out=pair_G[self.B:])
+                x = x_raw = self._real(feed, "x_G", out=None if self.aug else pair_G[self.B:])
+                if self.aug:
+                    # T(G(z)) carries autograd back into G; fake first, then real (the BN call order)
+                    u_aug = self._aug_u(feed, "aug_G", 2)
+                    fake, x = self._augment_pair(fake, x, u_aug, None, pair_G)
+                    recG.update(aug=u_aug)
                 laid_out = (fake.data_ptr() == pair_G.data_ptr()
                             and x.data_ptr() == pair_G[self.B:].data_ptr())
                 y_all = D.forward_pair_G(fake, x, cat=pair_G if laid_out else None)
                 y_pred_fake, y_pred = y_all[:self.B], y_all[self.B:].detach()
-                recG.update(x=x, y_pred=y_pred)
+                recG.update(x=x_raw, y_pred=y_pred)
                 errG = loss_G_cat(kind, y_all)
             else:
+                x = None
+                if self.aug:
+                    # the draws keep the batched path's order: z, the real batch, augmentation
+                    if kind > 4:
+                        x = self._real(feed, "x_G")
+                    u_aug = self._aug_u(feed, "aug_G", 2 if kind > 4 else 1)
+                    fake = augment.apply(fake, u_aug[:self.B], self.aug)
+                    recG.update(aug=u_aug)
                 y_pred_fake = D(fake)
                 y_pred = None
                 if kind > 4:
-                    x = self._real(feed, "x_G")
+                    if x is None:
+                        x = self._real(feed, "x_G")
                     with torch.no_grad():
-                        y_pred = D(x)
+                        y_pred = D(augment.apply(x, u_aug[self.B:], self.aug) if self.aug else x)
                     recG.update(x=x, y_pred=y_pred)
                 errG = loss_G(kind, y_pred_fake, y_pred)
             self._arm(self.redG)
