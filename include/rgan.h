@@ -28,7 +28,8 @@ extern "C" {
 /* ABI revision.  2: rgan_adam_packed takes step = device float[2] (step[1] is the
  * call's uint32 arrival ticket, zero before the first call); revision 1 took float[1].
  * 3: adds rgan_conv_wgrad_rows.  4: adds rgan_bn_segment_apply and rgan_bn_backward_sums_apply.
- * rgan_diffaug_workspace and rgan_diffaug are additive within revision 4 (nothing else changed). */
+ * rgan_diffaug_workspace, rgan_diffaug and rgan_ema_update are additive within revision 4 (nothing
+ * else changed). */
 #define RGAN_ABI_VERSION 4
 
 /* Activation codes fused into epilogues (GLI:345,370,388,417,437,450; SELU GLI:338). */
@@ -487,6 +488,24 @@ int rgan_gather_images(const float* images, const long long* idx, int batch, lon
 size_t rgan_diffaug_workspace(int batch, int channels, int h, int w);
 int rgan_diffaug(const float* x, const float* u, int batch, int channels, int h, int w, int policy,
                  int adjoint, float* ws, float* y, void* stream);
+
+/* ---- exponential moving average of G's weights (--rgan_ema_G; no reference counterpart) ----
+ * (additive within ABI revision 4: no existing entry point changed)
+ * One call, over ntensors pairs (avg[j], params[j]) of numel[j] floats each:
+ *   count[0] += 1;  t = count[0];
+ *   beta_t = warmup ? min(beta, (1 + t) / (10 + t)) : beta          (double; the TF num_updates ramp)
+ *   w = (float)(1 - beta_t);  avg = avg + w (params - avg)          (fp32, every element)
+ * rounded as torch.lerp rounds: fma(w, params - avg, avg) for w < 1/2, fma(w - 1, params - avg,
+ * params) otherwise, so w = 1 stores params itself.  hyper = device double[2] {beta, warmup (0 | 1)};
+ * count = device float[1].  Both are read on the device at run time: a call captured in a HIP
+ * graph follows the counter across replays, and a beta written into hyper between replays.
+ * avg, params, numel: host arrays of device pointers / sizes (numel[j] >= 0).  params is only
+ * read.  float4 accesses where avg[j] and params[j] are both 16-byte aligned, one float per lane
+ * for other tensors and for a tail of numel[j] % 4.  12 B/element of HBM traffic.  Launches: the
+ * one-thread count bump (rgan_adam_step_inc), then one per 48 tensors.  ntensors = 0: success,
+ * nothing launched, count unchanged. */
+int rgan_ema_update(int ntensors, float* const* avg, const float* const* params,
+                    const long long* numel, const double* hyper, float* count, void* stream);
 
 /* ---- live launch timing (bench.py roofline) ----
  * rgan_profile_begin(capacity): bracket each subsequent conv GEMM launch with HIP events

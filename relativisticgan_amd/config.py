@@ -6,9 +6,11 @@ order, bit-compatible inputs; ``device``: draw on the GPU, for throughput runs) 
 ``--rgan_sync_bn`` (BatchNorm statistics under data parallelism: default off = the
 reference's DataParallel, each rank normalises with its own shard; on = SyncBN over the
 global batch), ``--rgan_diffaug`` (differentiable augmentation of D's inputs, off by
-default; relativisticgan_amd/augment.py), ``--rgan_pac 2`` (the PacGAN-2 script,
-code/GAN_losses_iter_PAC.py, which shares this CLI) and ``--rgan_script`` (the defaults of
-GAN_losses_iter / GAN_losses_iter_art / GAN_losses_iter_PAC).
+default; relativisticgan_amd/augment.py), ``--rgan_ema_G BETA`` with ``--rgan_ema_warmup``
+(an exponential moving average of G's weights, kept next to G, checkpointed, sampled and used
+for the extra images; 0 = off, the default; relativisticgan_amd/ema.py), ``--rgan_pac 2``
+(the PacGAN-2 script, code/GAN_losses_iter_PAC.py, which shares this CLI) and
+``--rgan_script`` (the defaults of GAN_losses_iter / GAN_losses_iter_art / GAN_losses_iter_PAC).
 """
 import argparse
 
@@ -75,6 +77,12 @@ def make_parser(script="GAN_losses_iter"):
                    help="differentiable augmentation of every image D sees, reals and fakes, with G's gradient "
                         "flowing back through it: a comma-separated subset of color,translation,cutout "
                         "(default '': off; not with --rgan_pac 2)")
+    p.add_argument("--rgan_ema_G", type=float, default=0.0,
+                   help="keep an exponential moving average of G's weights with this decay, in [0, 1) (e.g. "
+                        "0.999): checkpointed as G_ema, sampled next to G's own sample grid and used for the "
+                        "extra images (default 0: off)")
+    p.add_argument("--rgan_ema_warmup", type="bool", default=True,
+                   help="ramp the moving average's decay as min(beta, (1 + t) / (10 + t)) over its first updates")
     p.add_argument("--rgan_perf_log", type="bool", default=True,
                    help="after each reference log line, a line with img/s and MFMA%% of the training "
                         "iterations since the previous one (sample PNGs, checkpoints and extra images excluded)")
@@ -94,6 +102,8 @@ def parse(argv=None):
         validate(ns.rgan_diffaug, ns.pac)
     except ValueError as e:
         parser.error(str(e))  # exits with the message
+    if not 0.0 <= ns.rgan_ema_G < 1.0:
+        parser.error(f"--rgan_ema_G must lie in [0, 1) (0 = off), got {ns.rgan_ema_G}")
     return ns
 
 

@@ -133,13 +133,23 @@ class _PackCache:
         if ent[0]() is not None and self.entries.get(key) is ent:
             del self.entries[key]
 
+    def _snapshot(self):
+        """list(entries.items()).  Building the list allocates, an allocation can start a garbage
+        collection, and a collected weight's weak-reference callback (_drop) deletes its entry:
+        the dict then changes size under the iteration.  Taken again when that happens."""
+        while True:
+            try:
+                return list(self.entries.items())
+            except RuntimeError:
+                continue
+
     def refresh(self, params):
         """Repack, in one batched launch, every cached layout of ``params`` whose weight
         moved (called right after an optimizer step): the next convolutions find them
         current instead of packing one launch at a time."""
         ids = {id(p) for p in params}
         todo = []
-        for key, ent in list(self.entries.items()):
+        for key, ent in self._snapshot():
             base, w = ent[0](), self._weight(ent)
             if base is not None and w is None:
                 self._stale(key, ent)
@@ -167,7 +177,7 @@ class _PackCache:
         rgan_adam_packed, which rewrites them with the new values)."""
         idx = {id(p): i for i, p in enumerate(params)}
         out = []
-        for key, ent in list(self.entries.items()):
+        for key, ent in self._snapshot():
             base, w = ent[0](), self._weight(ent)
             if base is not None and w is None:
                 self._stale(key, ent)
@@ -1104,6 +1114,34 @@ def diffaug(x, u, policy, adjoint=False, out=None):
     L.check(lib.rgan_diffaug(L.ptr(x), L.ptr(u), B, C, H, W, int(policy), int(bool(adjoint)), L.ptr(ws), L.ptr(out),
                              L.stream()), "rgan_diffaug")
     return out
+
+
+# ------------------------------------------------------------------ moving average of G
+def ema_update(avgs, params, hyper, count):
+    """One moving-average step of include/rgan.h rgan_ema_update over the tensor pairs:
+    ``count += 1``, then ``avg = lerp(avg, p, 1 - beta_t)`` with beta_t from ``hyper`` (device
+    double[2] {beta, warmup}) and the new count (device float[1]).  An ``avg`` walks its ``p``
+    with one flat index, so it must share p's shape and strides (dense, any permutation)."""
+    if len(avgs) != len(params):
+        raise L.RganError(f"ema_update: {len(avgs)} averages for {len(params)} parameters")
+    L.require_cuda(hyper, count, *avgs, *params)
+    _f32(count, *avgs, *params)
+    if hyper.dtype != torch.float64 or hyper.numel() < 2 or count.numel() < 1:
+        raise L.RganError("ema_update: hyper must be float64[2] {beta, warmup} and count float32[1]")
+    for a, p in zip(avgs, params):
+        if a.shape != p.shape or a.stride() != p.stride():
+            raise L.RganError(f"ema_update: average {tuple(a.shape)} / {a.stride()} does not match its parameter "
+                              f"{tuple(p.shape)} / {p.stride()}")
+        if p.numel() and 1 + sum((s - 1) * st for s, st in zip(p.shape, p.stride())) != p.numel():
+            raise L.RganError("ema_update: tensors must be dense (the kernel walks numel floats of storage)")
+    n = len(params)
+    arr = ctypes.c_void_p * max(n, 1)
+    A = arr(*[a.data_ptr() for a in avgs])
+    P = arr(*[p.data_ptr() for p in params])
+    N = (ctypes.c_longlong * max(n, 1))(*[p.numel() for p in params])
+    L.check(L.lib().rgan_ema_update(n, ctypes.cast(A, ctypes.c_void_p), ctypes.cast(P, ctypes.c_void_p),
+                                    ctypes.cast(N, ctypes.c_void_p), L.ptr(hyper), L.ptr(count), L.stream()),
+            "rgan_ema_update")
 
 
 # ------------------------------------------------------------------ GEMM arithmetic

@@ -24,6 +24,7 @@ dispatcher-level tracers see the MI355X kernels as graph nodes (not opaque Pytho
   rgan::diffaug          colour / translation / cutout of D's inputs (--rgan_diffaug; not in the reference)
   rgan::diffaug_backward its adjoint
   rgan::adam_            torch.optim.Adam's single-tensor step (mutating)          GLI:659,712
+  rgan::ema_update_      moving average of G's weights (--rgan_ema_G, mutating; not in the reference)
 
 Differentiability: every op above has a first-order formula; conv2d / conv2d_dgrad /
 conv2d_wgrad and act_backward of the piecewise-linear activations (ReLU, LeakyReLU, none) are
@@ -510,6 +511,20 @@ def _(params, grads, exp_avgs, exp_avg_sqs, hyper, step):
     return None
 
 
+# ------------------------------------------------------------------ moving average of G
+@torch.library.custom_op("rgan::ema_update_", mutates_args=("avgs", "count"), device_types=_DEV)
+def ema_update_(avgs: List[torch.Tensor], params: List[torch.Tensor], hyper: torch.Tensor,
+                count: torch.Tensor) -> None:
+    """One step of the moving average of ``params`` (hyper = double[2] {beta, warmup}, count =
+    float[1] incremented first; include/rgan.h rgan_ema_update)."""
+    K.ema_update(avgs, params, hyper, count)
+
+
+@ema_update_.register_fake
+def _(avgs, params, hyper, count):
+    return None
+
+
 # ------------------------------------------------------------------ traced layers (nets)
 def tracing(t):
     """A trace (torch.export / torch.compile / fake-tensor propagation) rather than a run."""
@@ -541,4 +556,5 @@ def layer_forward(layer, h, training):
 
 OPS = ("conv2d", "conv2d_dgrad", "conv2d_wgrad", "channel_sum", "act_backward", "batch_norm_stats_",
        "batch_norm_apply", "batch_norm_backward", "spectral_power_", "spectral_scale", "spectral_backward", "loss_head",
-       "loss_head_grad", "gp_penalty", "gp_penalty_backward", "diffaug", "diffaug_backward", "adam_")
+       "loss_head_grad", "gp_penalty", "gp_penalty_backward", "diffaug", "diffaug_backward", "adam_",
+       "ema_update_")

@@ -8,7 +8,9 @@ the reference's RNG consumption order when ``rgan_rng == 'ho
 
 Run as a script it is the reference CLI (``python -m relativisticgan_amd.train --loss_D 7 ...``)
 with synthetic images (``--rgan_synthetic N``; torchvision / image folders are out of
-scope), the same log line (GLI:723) and the same checkpoint dict (GLI:737-747).
+scope), the same log line (GLI:723) and the same checkpoint dict (GLI:737-747).  With
+``--rgan_ema_G`` an average of G's weights (relativisticgan_amd/ema.py) follows every G
+optimizer step, is checkpointed under one more key, ``G_ema``, and draws a second sample grid.
 """
 import os
 import random
@@ -20,6 +22,7 @@ import torch
 
 from . import augment, autograd, dp
 from .config import TITLES, parse
+from .ema import GeneratorEMA
 from .kernels import DeviceRNG
 from .losses import gradient_penalty, loss_D, loss_D_cat, loss_D_fake, loss_D_real, loss_G, loss_G_cat, unit_seed
 from .nets import DCGAN_D, DCGAN_G, weights_init
@@ -76,6 +79,10 @@ class Trainer:
         self.G.to(self.device)
         self.D.to(self.device)
         self.z_test = self._shard(z_test).to(self.device)
+        # --rgan_ema_G: the moving average of G's weights (None = off: no second net, no call)
+        ema_beta = getattr(p, "rgan_ema_G", 0.0) or 0.0
+        self.ema = (GeneratorEMA(self.G, p, ema_beta, warmup=getattr(p, "rgan_ema_warmup", True))
+                    if ema_beta > 0 else None)
         self.optD = Adam(self.D.parameters(), lr=p.lr_D, betas=(p.beta1, p.beta2), weight_decay=p.weight_decay)
         self.optG = Adam(self.G.parameters(), lr=p.lr_G, betas=(p.beta1, p.beta2), weight_decay=p.weight_decay)
         self.decayD = torch.optim.lr_scheduler.ExponentialLR(self.optD, gamma=1 - p.decay)
@@ -394,6 +401,8 @@ class Trainer:
         if hooks:
             hooks("G", recG)
         self.optG.step()
+        if self.ema is not None:
+            self.ema.update()  # follows the real step: deferred, captured or eager, once per Giters
         if hooks:
             hooks("G.post", recG)
 
@@ -416,10 +425,13 @@ class Trainer:
                                "host-side Adam step counts and LR schedulers are stale; checkpoint an eagerly "
                                "stepped trainer")
         self.flush()
-        return {"i": i, "current_set_images": current_set_images, "G_state": self.G.state_dict(),
-                "D_state": self.D.state_dict(), "G_optimizer": self.optG.state_dict(),
-                "D_optimizer": self.optD.state_dict(), "G_scheduler": self.decayG.state_dict(),
-                "D_scheduler": self.decayD.state_dict(), "z_test": _gather_batch(self.z_test)}
+        st = {"i": i, "current_set_images": current_set_images, "G_state": self.G.state_dict(),
+              "D_state": self.D.state_dict(), "G_optimizer": self.optG.state_dict(),
+              "D_optimizer": self.optD.state_dict(), "G_scheduler": self.decayG.state_dict(),
+              "D_scheduler": self.decayD.state_dict(), "z_test": _gather_batch(self.z_test)}
+        if self.ema is not None:  # (off: exactly the reference's keys)
+            st["G_ema"] = self.ema.state_dict()
+        return st
 
     def load(self, ckpt):
         self.flush()
@@ -429,6 +441,11 @@ class Trainer:
         self.optD.load_state_dict(ckpt["D_optimizer"])
         self.decayG.load_state_dict(ckpt["G_scheduler"])
         self.decayD.load_state_dict(ckpt["D_scheduler"])
+        if self.ema is not None:
+            if "G_ema" in ckpt:
+                self.ema.load_state_dict(ckpt["G_ema"])
+            else:  # written by the reference or with the flag off: average from the loaded G on
+                self.ema.restart()
         self.z_test.copy_(self._shard(ckpt["z_test"].to(self.device)) if ckpt["z_test"].shape[0] != self.B
                           else ckpt["z_test"])
         return ckpt["i"], ckpt["current_set_images"]
@@ -560,6 +577,14 @@ def main(argv=None):
             grid = _gather_batch(t.fake_test)
             if lead:
                 save_image(grid, os.path.join(base, "images", "fake_samples_iter%05d.png" % i), normalize=True)
+            if t.ema is not None:
+                # the same z_test through the averaged weights, after this iteration's update
+                t.flush()
+                with torch.no_grad():
+                    grid = _gather_batch(t.ema.generator()(t.z_test))
+                if lead:
+                    save_image(grid, os.path.join(base, "images", "fake_samples_ema_iter%05d.png" % i),
+                               normalize=True)
             output_done(t_out)
         if (i + 1) % p.print_every == 0:
             say(t.log_line(i, time.time() - start))  # the reference's line, unchanged (GLI:723-726)
@@ -578,7 +603,8 @@ def main(argv=None):
                     say("Models saved")
             if p.gen_extra_images > 0:
                 t.flush()
-                generate_extra_images(t.G, p, "%s/%01d/" % (p.extra_folder, current_set_images))
+                generate_extra_images(t.G if t.ema is None else t.ema.generator(), p,
+                                      "%s/%01d/" % (p.extra_folder, current_set_images))
             output_done(t_out)
     t.flush()
     if log:
