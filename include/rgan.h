@@ -395,6 +395,25 @@ int rgan_gp_penalty_backward(const float* g, const float* norms, int batch, long
                              float lam, int n_global, const float* gscale, float* dg,
                              void* stream);
 
+/* ---- zero-centred gradient penalties R1 / R2 (--rgan_r1, --rgan_r2; not in the reference) ----
+ * g: [batch][per] gradient image of D at the penalised point, contiguous.  batch <= 65535
+ * (the forward's grid puts the sample index in its y dimension), n_global >= batch.
+ * Forward: sq[b] = ||g_b||_2^2 and loss[0] = gamma / 2 * (sum_b sq[b]) / n_global, as a
+ * two-stage sum in a fixed order (no atomics, no counters: two calls give the same bits):
+ * stage 1 splits every sample over enough blocks to fill the chip, stage 2 adds each
+ * sample's partials and then the samples in index order, in double.  16-byte loads when
+ * per % 4 == 0 and g is 16-byte aligned; any per and any 4-byte alignment otherwise.
+ * ws: rgan_gp_zc_workspace(batch, per) bytes (0 for arguments the calls reject). */
+size_t rgan_gp_zc_workspace(int batch, long long per);
+int rgan_gp_zc_penalty(const float* g, int batch, long long per, float gamma, int n_global,
+                       float* sq, float* loss, void* ws, void* stream);
+/* dg = (gscale ? *gscale : 1) * gamma / n_global * g.  gscale (nullable) is a device
+ * scalar read by the kernel, so a captured call follows it.  dg may be g itself (each
+ * element is read, then written); a partial overlap is not supported.  16-byte accesses
+ * when per % 4 == 0 and both g and dg are 16-byte aligned. */
+int rgan_gp_zc_penalty_backward(const float* g, int batch, long long per, float gamma,
+                                int n_global, const float* gscale, float* dg, void* stream);
+
 /* ---- spectral norm (torch/nn/utils/spectral_norm.py:62-139; GLI call sites 334-446) ----
  * W viewed as [rows][cols]; element (r, c) sits at r*rs + (c / lo)*hs + (c % lo).
  * Conv2d weight (dim 0): rs = cin*kk, hs = kk, lo = kk.  ConvTranspose2d (dim 1, the

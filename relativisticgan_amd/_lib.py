@@ -116,6 +116,9 @@ _SIGS = {
     "rgan_gp_interp": (c_int, [c_vp, c_vp, c_vp, c_int, c_ll, c_vp, c_vp]),
     "rgan_gp_penalty": (c_int, [c_vp, c_int, c_ll, c_f, c_int, c_vp, c_vp, c_vp]),
     "rgan_gp_penalty_backward": (c_int, [c_vp, c_vp, c_int, c_ll, c_f, c_int, c_vp, c_vp, c_vp]),
+    "rgan_gp_zc_workspace": (c_sz, [c_int, c_ll]),
+    "rgan_gp_zc_penalty": (c_int, [c_vp, c_int, c_ll, c_f, c_int, c_vp, c_vp, c_vp, c_vp]),
+    "rgan_gp_zc_penalty_backward": (c_int, [c_vp, c_int, c_ll, c_f, c_int, c_vp, c_vp, c_vp]),
     "rgan_spectral_ws_bytes": (c_sz, [c_int, c_int]),
     "rgan_spectral_power": (c_int, [c_vp, c_int, c_int, c_ll, c_ll, c_int, c_f, c_vp, c_vp, c_vp, c_int, c_vp,
                                     c_vp]),

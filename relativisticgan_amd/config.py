@@ -8,7 +8,11 @@ reference's DataParallel, each rank normalises with its own shard; on = SyncBN o
 global batch), ``--rgan_diffaug`` (differentiable augmentation of D's inputs, off by
 default; relativisticgan_amd/augment.py), ``--rgan_ema_G BETA`` with ``--rgan_ema_warmup``
 (an exponential moving average of G's weights, kept next to G, checkpointed, sampled and used
-for the extra images; 0 = off, the default; relativisticgan_amd/ema.py), ``--rgan_pac 2``
+for the extra images; 0 = off, the default; relativisticgan_amd/ema.py), ``--rgan_r1 GAMMA`` /
+``--rgan_r2 GAMMA`` with ``--rgan_reg_every K`` (the zero-centred gradient penalties
+GAMMA / 2 * mean ||dD/dx||^2 on the real / on the generated batch D saw, added to the D step
+after errD and the WGAN-GP penalty; lazily every K-th iteration with weight GAMMA * K, see
+``reg_weight``; 0 = off, the default; not with --rgan_pac 2), ``--rgan_pac 2``
 (the PacGAN-2 script, code/GAN_losses_iter_PAC.py, which shares this CLI) and
 ``--rgan_script`` (the defaults of GAN_losses_iter / GAN_losses_iter_art / GAN_losses_iter_PAC).
 """
@@ -83,6 +87,14 @@ def make_parser(script="GAN_losses_iter"):
                         "extra images (default 0: off)")
     p.add_argument("--rgan_ema_warmup", type="bool", default=True,
                    help="ramp the moving average's decay as min(beta, (1 + t) / (10 + t)) over its first updates")
+    p.add_argument("--rgan_r1", type=float, default=0.0,
+                   help="zero-centred gradient penalty on the real batch D saw, R1 = GAMMA / 2 * mean "
+                        "||dD(x)/dx||^2, added to the D step (default 0: off; not with --rgan_pac 2)")
+    p.add_argument("--rgan_r2", type=float, default=0.0,
+                   help="the same penalty on the (detached) generated batch D saw, R2 (default 0: off)")
+    p.add_argument("--rgan_reg_every", type=int, default=1,
+                   help="lazy regularisation: run R1 / R2 in every K-th iteration only (i %% K == 0), with "
+                        "weight GAMMA * K (default 1: every iteration)")
     p.add_argument("--rgan_perf_log", type="bool", default=True,
                    help="after each reference log line, a line with img/s and MFMA%% of the training "
                         "iterations since the previous one (sample PNGs, checkpoints and extra images excluded)")
@@ -104,7 +116,32 @@ def parse(argv=None):
         parser.error(str(e))  # exits with the message
     if not 0.0 <= ns.rgan_ema_G < 1.0:
         parser.error(f"--rgan_ema_G must lie in [0, 1) (0 = off), got {ns.rgan_ema_G}")
+    try:
+        validate_reg(ns.rgan_r1, ns.rgan_r2, ns.rgan_reg_every, ns.pac)
+    except ValueError as e:
+        parser.error(str(e))
     return ns
+
+
+def validate_reg(r1, r2, every, pac=1):
+    """Check --rgan_r1 / --rgan_r2 / --rgan_reg_every (ValueError otherwise)."""
+    for name, gamma in (("--rgan_r1", r1), ("--rgan_r2", r2)):
+        if not gamma >= 0.0:
+            raise ValueError(f"{name} must be >= 0 (0 = off), got {gamma}")
+    if every < 1:
+        raise ValueError(f"--rgan_reg_every must be >= 1, got {every}")
+    if every > 1 and r1 == 0 and r2 == 0:
+        raise ValueError("--rgan_reg_every > 1 needs --rgan_r1 or --rgan_r2: it schedules those penalties only")
+    if (r1 > 0 or r2 > 0) and pac != 1:
+        raise ValueError("--rgan_r1 / --rgan_r2 are not available with --rgan_pac 2")
+
+
+def reg_weight(i, every, gamma):
+    """Lazy regularisation (--rgan_reg_every K): the weight of a zero-centred penalty in
+    iteration ``i`` -- gamma * K when i % K == 0 (the penalty then runs in each of that
+    iteration's D steps), else 0 (it does not run).  Stateless, so a resumed run continues the
+    schedule from its iteration number."""
+    return float(gamma) * every if gamma > 0 and i % every == 0 else 0.0
 
 
 def make_param(**overrides):

@@ -39,6 +39,11 @@ it normalises anything and the kernels get the global pixel count, while the aff
 gradients come from the rank's own (pre-all-reduce) sums -- the bucketed gradient
 all-reduce then sums them like every other gradient (include/rgan.h rgan_bn_dd_apply's
 *_local sums, rgan_bn_affine_grads).  No ATen arithmetic under either BatchNorm mode.
+
+The zero-centred penalties R1 / R2 (--rgan_r1 / --rgan_r2, not in the reference)
+run the same engine at another point with another head: D at the real (or the generated)
+batch itself instead of the interpolate, gp = gamma / 2 * mean ||g||^2 (rgan_gp_zc_penalty)
+and v = gamma / n * g (rgan_gp_zc_penalty_backward) -- the sweeps do not change.
 """
 import torch
 
@@ -86,18 +91,37 @@ def _global(sums):
 
 
 class GPEngine:
-    def __init__(self, D, x, x_fake, u, penalty):
+    """The penalty of one train-mode call of D.  Two things are parameters: the point D is
+    evaluated at, and the penalty's form.
+
+    Default (``point`` None): the WGAN-GP interpolate x*u + x_fake*(1-u) with the one-centred
+    form penalty * mean((||g|| - 1)^2) (GLI:646-658).
+    ``point`` given: D at that batch itself (copied into the pair buffer; no interpolation
+    kernel, no random number) with the zero-centred form penalty / 2 * mean ||g||^2 -- R1 at
+    the real batch, R2 at the generated one.  The three sweeps are the same either way; only
+    the head and the seed of sweep 1 differ."""
+
+    def __init__(self, D, x, x_fake, u, penalty, point=None):
         self.D, self.lam = D, float(penalty)
-        self.B = x.shape[0]
+        self.zero_centered = point is not None
+        ref = point if self.zero_centered else x
+        self.B = ref.shape[0]
         self.n_global = self.B * dp.world()
-        self.dev = x.device
+        self.dev = ref.device
         B = self.B
         # [adjoint; forward] image pair: v (the penalty's gradient) | x_hat
-        self.img = torch.empty((2 * B,) + tuple(x.shape[1:]), dtype=torch.float32, device=self.dev)
-        self.x_hat = K.gp_interp(x.detach(), x_fake.detach(), u.detach(), out=self.img[B:])
+        self.img = torch.empty((2 * B,) + tuple(ref.shape[1:]), dtype=torch.float32, device=self.dev)
+        if self.zero_centered:
+            self.x_hat = self.img[B:]
+            self.x_hat.copy_(point.detach())
+        else:
+            self.x_hat = K.gp_interp(x.detach(), x_fake.detach(), u.detach(), out=self.img[B:])
         self._forward()
         self._first_backward()
-        self.gp, self.norms, _ = K.gp_penalty(self.g, self.lam, self.n_global)
+        if self.zero_centered:
+            self.gp, self.norms, _ = K.gp_zc_penalty(self.g, self.lam, self.n_global)  # norms: ||g_b||^2, unused
+        else:
+            self.gp, self.norms, _ = K.gp_penalty(self.g, self.lam, self.n_global)
 
     # ------------------------------------------------------------ forward
     def _forward(self):
@@ -190,7 +214,11 @@ class GPEngine:
     def backward(self, dgp):
         B, recs = self.B, self.recs
         # v = dP/dg, in place over g in the image pair's first half (the penalty kept its norms)
-        ubar = K.gp_penalty_backward(self.g, self.norms, self.lam, self.n_global, dgp.contiguous(), out=self.img[:B])
+        if self.zero_centered:
+            ubar = K.gp_zc_penalty_backward(self.g, self.lam, self.n_global, dgp.contiguous(), out=self.img[:B])
+        else:
+            ubar = K.gp_penalty_backward(self.g, self.norms, self.lam, self.n_global, dgp.contiguous(),
+                                         out=self.img[:B])
         ydirs = [None] * len(recs)
         # sweep 1: up through the backward chain
         for li, r in enumerate(recs):
@@ -321,5 +349,14 @@ class _GPFn(torch.autograd.Function):
 def gradient_penalty(D, x, x_fake, u, penalty):
     """penalty * mean((||dD(x_hat)/dx_hat||_2 - 1)^2), x_hat = x*u + x_fake*(1-u) (GLI:648-657)."""
     eng = GPEngine(D, x, x_fake, u, penalty)
+    anchor = next(p for p in D.parameters() if p.requires_grad)
+    return _GPFn.apply(eng, anchor)
+
+
+def zero_centered_penalty(D, point, gamma):
+    """gamma / 2 * mean ||dD(point)/dpoint||_2^2 over the global batch: R1 at the real batch,
+    R2 at the (detached) generated one.  One more train-mode call of D, like the penalty above;
+    no gradient reaches ``point``."""
+    eng = GPEngine(D, None, None, None, gamma, point=point)
     anchor = next(p for p in D.parameters() if p.requires_grad)
     return _GPFn.apply(eng, anchor)

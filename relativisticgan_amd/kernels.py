@@ -944,6 +944,37 @@ def gp_penalty_backward(g, norms, lam, n_global, gscale, out=None):
     return dg
 
 
+def gp_zc_penalty(g, gamma, n_global):
+    """Zero-centred penalty head (R1 / R2): (gamma / 2 * sum_b ||g_b||^2 / n_global, the
+    per-sample squared norms, g as the kernel read it)."""
+    L.require_cuda(g)
+    g = g.contiguous()
+    B = g.shape[0]
+    per = g[0].numel()
+    sq = torch.empty(B, dtype=torch.float32, device=g.device)
+    loss = torch.empty((), dtype=torch.float32, device=g.device)
+    ws = L.workspace(L.lib().rgan_gp_zc_workspace(B, per), g.device)
+    L.check(L.lib().rgan_gp_zc_penalty(L.ptr(g), B, per, float(gamma), int(n_global), L.ptr(sq), L.ptr(loss),
+                                       L.ptr(ws), L.stream()), "rgan_gp_zc_penalty")
+    return loss, sq, g
+
+
+def gp_zc_penalty_backward(g, gamma, n_global, gscale, out=None):
+    """dZC/dg = gscale * gamma / n_global * g (gscale a device scalar, or None for 1).  ``out``
+    may be ``g`` itself (in place: each element is read before it is written)."""
+    L.require_cuda(g, gscale, out)
+    B = g.shape[0]
+    if not g.is_contiguous():
+        raise L.RganError("gp_zc_penalty_backward: g must be contiguous")
+    dg = torch.empty_like(g) if out is None else out
+    if not dg.is_contiguous() or dg.shape != g.shape:
+        raise L.RganError("gp_zc_penalty_backward: out must be contiguous and shaped like g")
+    L.check(L.lib().rgan_gp_zc_penalty_backward(L.ptr(g), B, g[0].numel(), float(gamma), int(n_global),
+                                                L.ptr(gscale), L.ptr(dg), L.stream()),
+            "rgan_gp_zc_penalty_backward")
+    return dg
+
+
 # ------------------------------------------------------------------ spectral norm
 def sn_view(w, transposed):
     """(rows, cols, rs, hs, lo) of torch's reshape_weight_to_matrix (dim 0 conv, dim 1 convT)."""

@@ -1,4 +1,5 @@
-"""The eight --loss_D heads and the WGAN-GP penalty as autograd ops on the HIP kernels.
+"""The eight --loss_D heads, the WGAN-GP penalty and the zero-centred R1 / R2 penalties as
+autograd ops on the HIP kernels.
 
 Heads (GLI:481-484 criteria; D side GLI:592-644; G side GLI:686-709):
   1 SGAN (BCE on D's sigmoid), 2 LSGAN, 3 WGAN(-GP), 4 HingeGAN: real and fake terms
@@ -235,3 +236,37 @@ def gradient_penalty_composite(D, x, x_fake, u, penalty):
     grad = torch.autograd.grad(outputs=out, inputs=x_both, grad_outputs=torch.ones_like(out),
                                retain_graph=True, create_graph=True, only_inputs=True)[0]
     return _GPPenalty.apply(grad, float(penalty), x.shape[0] * dp.world())
+
+
+# ---------------------------------------------------------------- zero-centred penalties (R1 / R2)
+class _ZCPenalty(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, g, gamma, n_global):
+        loss, _, gc = K.gp_zc_penalty(g, gamma, n_global)
+        ctx.gamma, ctx.n_global = gamma, n_global
+        ctx.save_for_backward(gc)
+        return loss
+
+    @staticmethod
+    def backward(ctx, gl):
+        gc, = ctx.saved_tensors
+        return K.gp_zc_penalty_backward(gc, ctx.gamma, ctx.n_global, gl.contiguous()), None, None
+
+
+def zero_centered_penalty(D, point, gamma):
+    """gamma / 2 * mean_b ||dD(point)/dpoint_b||_2^2 over the global batch: R1 with the real
+    batch as ``point``, R2 with the detached generated batch.  One more train-mode call of D
+    (BatchNorm running statistics and spectral vectors move, as for the WGAN-GP penalty); no
+    gradient flows to ``point`` and no random number is drawn.  Native engine (gp.py)."""
+    from . import gp as _gp
+    return _gp.zero_centered_penalty(D, point, gamma)
+
+
+def zero_centered_penalty_composite(D, point, gamma):
+    """The autograd form of the zero-centred penalty (create_graph through ConvLayerFn): the
+    engine's test reference."""
+    p = point.detach().clone().requires_grad_(True)
+    out = D(p)
+    grad = torch.autograd.grad(outputs=out, inputs=p, grad_outputs=torch.ones_like(out),
+                               retain_graph=True, create_graph=True, only_inputs=True)[0]
+    return _ZCPenalty.apply(grad, float(gamma), point.shape[0] * dp.world())

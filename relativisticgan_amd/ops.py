@@ -21,6 +21,8 @@ dispatcher-level tracers see the MI355X kernels as graph nodes (not opaque Pytho
   rgan::loss_head_grad
   rgan::gp_penalty       lam * mean((||g_b|| - 1)^2)                               GLI:646-658
   rgan::gp_penalty_backward
+  rgan::gp_zc_penalty    gamma / 2 * mean ||g_b||^2, the zero-centred R1 / R2 head (--rgan_r1, --rgan_r2; not in the reference)
+  rgan::gp_zc_penalty_backward
   rgan::diffaug          colour / translation / cutout of D's inputs (--rgan_diffaug; not in the reference)
   rgan::diffaug_backward its adjoint
   rgan::adam_            torch.optim.Adam's single-tensor step (mutating)          GLI:659,712
@@ -454,6 +456,49 @@ gp_penalty_backward.register_autograd(_no_double("gp_penalty_backward"),
                                       setup_context=lambda ctx, inputs, output: None)
 
 
+@torch.library.custom_op("rgan::gp_zc_penalty", mutates_args=(), device_types=_DEV)
+def gp_zc_penalty(g: torch.Tensor, gamma: float, n_global: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(gamma / 2 * sum_b ||g_b||_2^2 / n_global, the per-sample squared norms): the zero-centred
+    penalty head of R1 / R2 (include/rgan.h rgan_gp_zc_penalty)."""
+    loss, sq, _ = K.gp_zc_penalty(g, gamma, n_global)
+    return loss, sq
+
+
+@gp_zc_penalty.register_fake
+def _(g, gamma, n_global):
+    return torch.empty((), dtype=torch.float32, device=g.device), torch.empty(g.shape[0], dtype=torch.float32,
+                                                                              device=g.device)
+
+
+def _gp_zc_setup(ctx, inputs, output):
+    g, gamma, n_global = inputs
+    ctx.gamma, ctx.n_global = gamma, n_global
+    ctx.save_for_backward(g)
+
+
+def _gp_zc_backward(ctx, gl, gsq):
+    g, = ctx.saved_tensors
+    return torch.ops.rgan.gp_zc_penalty_backward(g, ctx.gamma, ctx.n_global, gl), None, None
+
+
+gp_zc_penalty.register_autograd(_gp_zc_backward, setup_context=_gp_zc_setup)
+
+
+@torch.library.custom_op("rgan::gp_zc_penalty_backward", mutates_args=(), device_types=_DEV)
+def gp_zc_penalty_backward(g: torch.Tensor, gamma: float, n_global: int, gl: torch.Tensor) -> torch.Tensor:
+    """gl * gamma / n_global * g (gl the upstream scalar gradient)."""
+    return K.gp_zc_penalty_backward(g.contiguous(), gamma, n_global, gl.reshape(1).contiguous())
+
+
+@gp_zc_penalty_backward.register_fake
+def _(g, gamma, n_global, gl):
+    return torch.empty(g.shape, dtype=torch.float32, device=g.device)
+
+
+gp_zc_penalty_backward.register_autograd(_no_double("gp_zc_penalty_backward"),
+                                         setup_context=lambda ctx, inputs, output: None)
+
+
 # ------------------------------------------------------------------ differentiable augmentation
 @torch.library.custom_op("rgan::diffaug", mutates_args=(), device_types=_DEV)
 def diffaug(x: torch.Tensor, u: torch.Tensor, policy: int) -> torch.Tensor:
@@ -556,5 +601,5 @@ def layer_forward(layer, h, training):
 
 OPS = ("conv2d", "conv2d_dgrad", "conv2d_wgrad", "channel_sum", "act_backward", "batch_norm_stats_",
        "batch_norm_apply", "batch_norm_backward", "spectral_power_", "spectral_scale", "spectral_backward", "loss_head",
-       "loss_head_grad", "gp_penalty", "gp_penalty_backward", "diffaug", "diffaug_backward", "adam_",
-       "ema_update_")
+       "loss_head_grad", "gp_penalty", "gp_penalty_backward", "gp_zc_penalty", "gp_zc_penalty_backward", "diffaug",
+       "diffaug_backward", "adam_", "ema_update_")

@@ -6,6 +6,8 @@ ran them.
 """
 import torch
 
+from .config import reg_weight
+
 FP32_MFMA_PEAK = 157.3e12  # MI355X_MICROARCH.md: Peak FP32 (matrix) = vector peak
 
 
@@ -17,7 +19,9 @@ def conv_flops_per_iteration(t):
       heads 1-4: the G step has no D(x): 8 F_D + 4 F_G - 2 d0 - g0;
       gradient penalty (GLI:646-658): + D(x_hat) fwd, its create-graph dgrad chain, and the
         double backward (adjoint conv fwd + wgrad per dgrad, then wgrad + dgrad back through
-        the forward): 6 F_D - d0 - 3 F_end."""
+        the forward): 6 F_D - d0 - 3 F_end;
+      zero-centred penalties (--rgan_r1, --rgan_r2): the gradient penalty's term once for each
+        that is on, amortised over the lazy period: (6 F_D - d0 - 3 F_end) / --rgan_reg_every."""
     def layer_flops(net, x_shape):
         out, h = [], torch.zeros(x_shape, device="meta")
         for layer in net._plan:
@@ -45,6 +49,13 @@ def conv_flops_per_iteration(t):
         total -= sum(fd)
     if p.loss_D == 3 or p.grad_penalty:
         total += 6 * sum(fd) - fd[0] - 3 * fd[-1]
+    # --rgan_r1 / --rgan_r2: the same engine pass each, in one iteration of every --rgan_reg_every
+    # (config.reg_weight names the iterations of a period that run them)
+    every = getattr(p, "rgan_reg_every", 1) or 1
+    for gamma in (getattr(p, "rgan_r1", 0.0) or 0.0, getattr(p, "rgan_r2", 0.0) or 0.0):
+        runs = sum(1 for i in range(every) if reg_weight(i, every, gamma))
+        if runs:
+            total += (6 * sum(fd) - fd[0] - 3 * fd[-1]) * runs / every
     return total
 
 

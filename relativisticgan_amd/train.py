@@ -11,6 +11,9 @@ with synthetic images (``--rgan_synthetic N``; torchvision / image folders are o
 scope), the same log line (GLI:723) and the same checkpoint dict (GLI:737-747).  With
 ``--rgan_ema_G`` an average of G's weights (relativisticgan_amd/ema.py) follows every G
 optimizer step, is checkpointed under one more key, ``G_ema``, and draws a second sample grid.
+With ``--rgan_r1`` / ``--rgan_r2`` the D step ends with the zero-centred gradient penalties on
+the real / generated batch D saw (after errD and the WGAN-GP penalty), in the iterations
+``--rgan_reg_every`` names (config.reg_weight).
 """
 import os
 import random
@@ -21,10 +24,11 @@ import numpy
 import torch
 
 from . import augment, autograd, dp
-from .config import TITLES, parse
+from .config import TITLES, parse, reg_weight, validate_reg
 from .ema import GeneratorEMA
 from .kernels import DeviceRNG
-from .losses import gradient_penalty, loss_D, loss_D_cat, loss_D_fake, loss_D_real, loss_G, loss_G_cat, unit_seed
+from .losses import (gradient_penalty, loss_D, loss_D_cat, loss_D_fake, loss_D_real, loss_G, loss_G_cat, unit_seed,
+                     zero_centered_penalty)
 from .nets import DCGAN_D, DCGAN_G, weights_init
 from .optim import Adam
 from .perf import ThroughputMeter
@@ -105,6 +109,12 @@ class Trainer:
         self.pac = getattr(p, "pac", 1)  # 2: code/GAN_losses_iter_PAC.py
         # --rgan_diffaug: the kernel's policy mask (0 = off: no call, no draw)
         self.aug = augment.validate(getattr(p, "rgan_diffaug", ""), self.pac)
+        # --rgan_r1 / --rgan_r2 / --rgan_reg_every: the zero-centred penalties' gammas and their
+        # lazy period (0 = off: no extra D call, nothing launched)
+        self.r1 = float(getattr(p, "rgan_r1", 0.0) or 0.0)
+        self.r2 = float(getattr(p, "rgan_r2", 0.0) or 0.0)
+        self.reg_every = int(getattr(p, "rgan_reg_every", 1) or 1)
+        validate_reg(self.r1, self.r2, self.reg_every, self.pac)
         # one batched D pass per D step where the nets allow it (--rgan_batch_D).  Default
         # (auto): on, under data parallelism too.  G's gradient buckets all-reduce while G's
         # own backward runs (GradReducer), so the deferred G step (flush, right before the
@@ -230,6 +240,10 @@ class Trainer:
         p, D, G = self.p, self.D, self.G
         kind = p.loss_D
         gp_on = kind == 3 or p.grad_penalty
+        # this iteration's R1 / R2 weights (0 = the penalty does not run: config.reg_weight)
+        w_r1, w_r2 = reg_weight(i, self.reg_every, self.r1), reg_weight(i, self.reg_every, self.r2)
+        # the D step's last backward -- the one the gradient all-reduce overlaps (redD armed before it)
+        last_bwd = "r2" if w_r2 else ("r1" if w_r1 else ("gp" if gp_on else "errD"))
         zshape = (p.batch_size * self.pac, p.z_size, 1, 1)
         if i % p.print_every == 0:
             self.flush()
@@ -271,7 +285,7 @@ class Trainer:
                 # heads 1-4: err_real.backward(); err_fake.backward() accumulate = one backward
                 # of the sum (GLI:605, 624); heads 5-8: errD.backward() (GLI:644)
                 errD = loss_D_cat(kind, y_all)
-                if not gp_on:
+                if last_bwd == "errD":
                     self._arm(self.redD)
                 self._backward(errD)
                 errD = errD.detach()
@@ -287,7 +301,7 @@ class Trainer:
                     x_fake = augment.apply(x_fake, u_aug[self.B:], self.aug)
                 y_pred_fake = D(x_fake)
                 err_fake = loss_D_fake(kind, y_pred_fake)
-                if not gp_on:
+                if last_bwd == "errD":
                     self._arm(self.redD)
                 self._backward(err_fake)
                 errD = err_real.detach() + err_fake.detach()
@@ -301,7 +315,7 @@ class Trainer:
                     x_fake = augment.apply(x_fake, u_aug[self.B:], self.aug)
                 y_pred_fake = D(x_fake)
                 errD = loss_D(kind, y_pred, y_pred_fake)
-                if not gp_on:
+                if last_bwd == "errD":
                     self._arm(self.redD)
                 self._backward(errD)
             rec = {"x": x_raw, "z": z, "y_pred": y_pred.detach(), "y_pred_fake": y_pred_fake.detach(),
@@ -312,9 +326,19 @@ class Trainer:
                 # with augmentation on, x and x_fake are the transformed batches: what D saw
                 u = self._uniform(feed, "u", (p.batch_size, 1, 1, 1))
                 gp = gradient_penalty(D, x, x_fake, u, p.penalty)
-                self._arm(self.redD)
+                if last_bwd == "gp":
+                    self._arm(self.redD)
                 self._backward(gp)
                 rec.update(u=u, gp=gp.detach())
+            # zero-centred penalties on the batches D saw (transformed ones under --rgan_diffaug),
+            # each one more train-mode call of D, added into D's .grad: R1 (real), then R2 (fake)
+            for key, w, point in (("r1", w_r1, x), ("r2", w_r2, x_fake)):
+                if w:
+                    pen = zero_centered_penalty(D, point, w)
+                    if last_bwd == key:
+                        self._arm(self.redD)
+                    self._backward(pen)
+                    rec[key] = pen.detach()
             if self.redD is not None:
                 self.redD.finish()
             if hooks:
