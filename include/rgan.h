@@ -362,7 +362,9 @@ int rgan_bn_affine_grads(const double* sums, const float* stats, int C, float* d
 /* ---- loss heads (GLI:481-484, 592-644, 686-709) ----
  * kind = --loss_D (1..8); side 0 = D-real (heads 1-4) / D (heads 5-8), 1 = D-fake
  * (heads 1-4), 2 = G.  r, f: [n] (either nullable per head).  loss: device float[1];
- * dr, df: [n] gradients of loss w.r.t. r and f (nullable).  n <= 65536. */
+ * dr, df: [n] gradients of loss w.r.t. r and f (nullable).  n <= 65536.  The per-element
+ * terms are fp32.  The loss sums of heads 1-4 (whose gradients depend on no sum) are
+ * accumulated in double and rounded once; heads 5-8 sum in fp32. */
 int rgan_loss_head(int kind, int side, const float* r, const float* f, int n,
                    float* loss, float* dr, float* df, void* stream);
 /* Heads 1-4, D side as ONE launch: loss3 = {errD_real, errD_fake, errD_real + errD_fake}

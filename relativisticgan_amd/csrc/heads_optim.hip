@@ -65,6 +65,11 @@ __device__ __forceinline__ float single_term(int kind, int side, float t, float&
 
 // phase < 0: everything in one launch (single process).  Otherwise the distributed phases
 // of rgan_loss_head_dist.  One workgroup of 1024 threads.
+// Heads 1-4: the terms are fp32, their sum over the batch is accumulated in double -- the
+// loss may be a small difference of large terms (a WGAN mean over logits of opposite signs or
+// with a common offset), which an fp32 sum loses to its order of summation; their gradients
+// do not depend on any sum.  Heads 5-8 sum in fp32: their gradients depend on the
+// relativistic means, so the order of those sums is part of what a training step computes.
 __global__ __launch_bounds__(1024) void loss_head_kernel(int kind, int side, int phase, const float* r,
                                                          const float* f, int n, int n_global,
                                                          const float* gsum, float* sums, float* loss,
@@ -75,18 +80,19 @@ __global__ __launch_bounds__(1024) void loss_head_kernel(int kind, int side, int
   if (zr)  // rgan_loss_head_joint: the joint gradient's no-grad half is zero
     for (int i = tid; i < n; i += blockDim.x) zr[i] = 0.f;
   if (kind <= 4) {
+    __shared__ double redd[16];
     const float* t = side == 0 ? r : f;
     float* dt = side == 0 ? dr : df;
-    float s = 0.f;
+    double s = 0.0;
     for (int i = tid; i < n; i += blockDim.x) {
       float der;
-      s += single_term(kind, side, t[i], der);
+      s += (double)single_term(kind, side, t[i], der);
       if (dt && phase != 0) dt[i] = der / ng;
     }
-    s = block_sum(s, red);
+    s = block_sum_d(s, redd);
     if (tid == 0) {
-      if (phase < 0) loss[0] = s / ng;
-      else if (phase == 0) sums[0] = s;
+      if (phase < 0) loss[0] = (float)(s / (double)n_global);
+      else if (phase == 0) sums[0] = (float)s;
       else if (loss) loss[0] = gsum[0] / ng;
     }
     return;
@@ -171,24 +177,24 @@ __global__ __launch_bounds__(1024) void loss_head_pair_kernel(int kind, const fl
                                                               const float* __restrict__ f, int n,
                                                               float* __restrict__ loss3, float* __restrict__ dr,
                                                               float* __restrict__ df) {
-  __shared__ float red[16];
+  __shared__ double red[16];
   const int tid = threadIdx.x;
   const float ng = (float)n;
-  float sr = 0.f, sf = 0.f;
+  double sr = 0.0, sf = 0.0;
   for (int i = tid; i < n; i += blockDim.x) {
     float der;
-    sr += single_term(kind, 0, r[i], der);
+    sr += (double)single_term(kind, 0, r[i], der);
     if (dr) dr[i] = der / ng;
-    sf += single_term(kind, 1, f[i], der);
+    sf += (double)single_term(kind, 1, f[i], der);
     if (df) df[i] = der / ng;
   }
-  sr = block_sum(sr, red);
-  sf = block_sum(sf, red);
+  sr = block_sum_d(sr, red);
+  sf = block_sum_d(sf, red);
   if (tid == 0) {
-    const float lr = sr / ng, lf = sf / ng;
-    loss3[0] = lr;
-    loss3[1] = lf;
-    loss3[2] = lr + lf;
+    const double lr = sr / (double)n, lf = sf / (double)n;
+    loss3[0] = (float)lr;
+    loss3[1] = (float)lf;
+    loss3[2] = (float)(lr + lf);  // the sum before rounding: real and fake terms may cancel (WGAN)
   }
 }
 

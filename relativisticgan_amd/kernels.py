@@ -851,9 +851,33 @@ def channel_sum(t, out, accumulate=False):
 
 
 # ------------------------------------------------------------------ loss heads / GP
+HEAD_MAX_N = 65536  # one workgroup strides over the batch (include/rgan.h)
+
+
+def _head_check(what, n, exact=(), gsum=None, gsum_min=0):
+    """The head kernels take raw pointers and one count ``n``: every tensor handed to them must
+    be float32 and contiguous, each (name, tensor, count) of ``exact`` must hold exactly
+    ``count`` elements and ``gsum`` at least ``gsum_min``.  Pure Python, before any pointer is
+    taken; a None tensor is an argument not given."""
+    if not 1 <= n <= HEAD_MAX_N:
+        raise L.RganError(f"{what}: n = {n} is outside 1 .. {HEAD_MAX_N}")
+    for name, t, count in tuple(exact) + (("gsum", gsum, None),):
+        if t is None:
+            continue
+        if t.dtype != torch.float32:
+            raise L.RganError(f"{what}: {name} must be float32 (got {t.dtype})")
+        if not t.is_contiguous():
+            raise L.RganError(f"{what}: {name} must be contiguous")
+        if count is not None and t.numel() != count:
+            raise L.RganError(f"{what}: {name} has {t.numel()} elements, expected {count}")
+    if gsum is not None and gsum.numel() < gsum_min:
+        raise L.RganError(f"{what}: gsum has {gsum.numel()} elements, expected at least {gsum_min}")
+
+
 def loss_head(kind, side, r, f, need_dr=True, need_df=True, dr=None, df=None):
     t = r if r is not None else f
     n = t.numel()
+    _head_check("loss_head", n, (("r", r, n), ("f", f, n), ("dr", dr, n), ("df", df, n)))
     loss = torch.empty((), dtype=torch.float32, device=t.device)
     if dr is None:
         dr = torch.empty_like(r) if (r is not None and need_dr) else None
@@ -866,22 +890,27 @@ def loss_head(kind, side, r, f, need_dr=True, need_df=True, dr=None, df=None):
 
 def loss_head_pair(kind, r, f, need_dr=True, need_df=True, dr=None, df=None):
     """Heads 1-4 D side: (loss3 = [real, fake, sum], dr, df) in one launch."""
+    n = r.numel()
+    _head_check("loss_head_pair", n, (("r", r, n), ("f", f, n), ("dr", dr, n), ("df", df, n)))
     loss3 = torch.empty(3, dtype=torch.float32, device=r.device)
     if dr is None and need_dr:
         dr = torch.empty_like(r)
     if df is None and need_df:
         df = torch.empty_like(f)
-    L.check(L.lib().rgan_loss_head_pair(int(kind), L.ptr(r), L.ptr(f), r.numel(), L.ptr(loss3), L.ptr(dr),
+    L.check(L.lib().rgan_loss_head_pair(int(kind), L.ptr(r), L.ptr(f), n, L.ptr(loss3), L.ptr(dr),
                                         L.ptr(df), L.stream()), "rgan_loss_head_pair")
     return loss3, dr, df
 
 
-def loss_head_joint(kind, y):
+def loss_head_joint(kind, y, out=None):
     """Heads 5-8, G side, on the joint [D(G(z)); D(x)] output: (loss, dy) with dy's second
-    half zero (rgan_loss_head_joint)."""
+    half zero (rgan_loss_head_joint).  ``out`` receives dy (2n float32, contiguous)."""
+    if y.numel() % 2:
+        raise L.RganError(f"loss_head_joint: y has {y.numel()} elements, expected an even count [f; r]")
     n = y.numel() // 2
+    _head_check("loss_head_joint", n, (("y", y, 2 * n), ("out", out, 2 * n)))
     loss = torch.empty((), dtype=torch.float32, device=y.device)
-    dy = torch.empty_like(y)
+    dy = torch.empty_like(y) if out is None else out
     L.check(L.lib().rgan_loss_head_joint(int(kind), L.ptr(y), n, L.ptr(loss), L.ptr(dy), L.stream()),
             "rgan_loss_head_joint")
     return loss, dy
@@ -890,6 +919,9 @@ def loss_head_joint(kind, y):
 def loss_head_dist(kind, side, phase, r, f, n_global, gsum=None, need_dr=True, need_df=True):
     t = r if r is not None else f
     n = t.numel()
+    # phase 1 reads the global (sum r, sum f); phase 2 the global loss sum (heads 1-5) or all six
+    _head_check("loss_head_dist", n, (("r", r, n), ("f", f, n)), gsum=gsum,
+                gsum_min=1 if kind <= 5 else 2 if phase == 1 else 6)
     sums = torch.zeros(4, dtype=torch.float32, device=t.device)
     loss = torch.empty((), dtype=torch.float32, device=t.device)
     dr = torch.empty_like(r) if (phase == 2 and r is not None and need_dr) else None

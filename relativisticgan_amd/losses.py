@@ -169,7 +169,7 @@ class _HeadCatG(torch.autograd.Function):
         else:
             loss, df = K.loss_head_joint(kind, y)  # [d errG / d D(G(z)); 0]
         ctx.save_for_backward(df)
-        ctx.B = B
+        ctx.B, ctx.shape = B, y.shape
         return loss
 
     @staticmethod
@@ -177,10 +177,10 @@ class _HeadCatG(torch.autograd.Function):
         df, = ctx.saved_tensors
         B = ctx.B
         if df.numel() == 2 * B and _is_unit(g):
-            return df, None
+            return df.view(ctx.shape), None
         out = torch.zeros(2 * B, dtype=df.dtype, device=df.device)
         K.scale(df[:B], g.contiguous(), out=out[:B])
-        return out, None
+        return out.view(ctx.shape), None  # y may be [2B, 1, 1, 1]
 
 
 def loss_G_cat(kind, y):

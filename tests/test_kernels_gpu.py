@@ -10,6 +10,8 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from tests.heads_ref import ref_head
+
 pytestmark = pytest.mark.gpu
 
 DEV = "cuda"
@@ -699,36 +701,6 @@ def _bn_epilogue_case(K, B, cin, cout, H, kgeo, tr, segs, expect_fused, bias):
         assert _rel(mom[cout:2 * cout], mean) < 1e-6 and _rel(mom[2 * cout:], var * n) < 1e-6
 
 
-def _torch_head(kind, side, r, f):
-    """The reference's expressions (GLI:592-709) in fp64 with torch autograd."""
-    ones = torch.ones_like(r if r is not None else f)
-    zeros = torch.zeros_like(ones)
-    bce, bcel = torch.nn.BCELoss(), torch.nn.BCEWithLogitsLoss()
-    relu = torch.nn.ReLU()
-    if kind <= 4:
-        t = r if side == 0 else f
-        if kind == 1:
-            return bce(t, zeros if side == 1 else ones)
-        if kind == 2:
-            return torch.mean(t ** 2) if side == 1 else torch.mean((t - ones) ** 2)
-        if kind == 3 or side == 2:
-            return torch.mean(t) if side == 1 else -torch.mean(t)
-        return torch.mean(relu(1.0 - t)) if side == 0 else torch.mean(relu(1.0 + t))
-    if kind == 5:
-        return bcel(r - f, ones) if side == 0 else bcel(f - r, ones)
-    if kind == 6:
-        if side == 0:
-            return (bcel(r - torch.mean(f), ones) + bcel(f - torch.mean(r), zeros)) / 2
-        return (bcel(r - torch.mean(f), zeros) + bcel(f - torch.mean(r), ones)) / 2
-    if kind == 7:
-        if side == 0:
-            return (torch.mean((r - torch.mean(f) - ones) ** 2) + torch.mean((f - torch.mean(r) + ones) ** 2)) / 2
-        return (torch.mean((r - torch.mean(f) + ones) ** 2) + torch.mean((f - torch.mean(r) - ones) ** 2)) / 2
-    if side == 0:
-        return (torch.mean(relu(1.0 - (r - torch.mean(f)))) + torch.mean(relu(1.0 + (f - torch.mean(r))))) / 2
-    return (torch.mean(relu(1.0 + (r - torch.mean(f)))) + torch.mean(relu(1.0 - (f - torch.mean(r))))) / 2
-
-
 HEAD_CASES = [(k, s) for k in (1, 2, 3, 4) for s in (0, 1, 2)] + [(k, s) for k in (5, 6, 7, 8) for s in (0, 2)]
 
 
@@ -745,15 +717,14 @@ def test_loss_heads(K, kind, side, n):
     needs_r = kind > 4 or side == 0
     needs_f = kind > 4 or side != 0
     loss, dr, df = K.loss_head(kind, side, r if needs_r else None, f if needs_f else None)
-    r64 = r.double().cpu().requires_grad_(True)
-    f64 = f.double().cpu().requires_grad_(True)
-    ref = _torch_head(kind, side, r64 if needs_r else None, f64 if needs_f else None)
-    ref.backward()
+    r64 = r.double().cpu()
+    f64 = f.double().cpu()
+    ref, r_grad, f_grad = ref_head(kind, side, r64 if needs_r else None, f64 if needs_f else None)
     assert abs(loss.item() - ref.item()) <= 1e-5 * max(1.0, abs(ref.item()))
     if needs_r:
-        assert _rel(dr, r64.grad) < 1e-5 or r64.grad.abs().max() < 1e-12
+        assert _rel(dr, r_grad) < 1e-5 or r_grad.abs().max() < 1e-12
     if needs_f:
-        assert _rel(df, f64.grad) < 1e-5 or f64.grad.abs().max() < 1e-12
+        assert _rel(df, f_grad) < 1e-5 or f_grad.abs().max() < 1e-12
 
 
 def test_gp_kernels(K):
