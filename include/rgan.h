@@ -28,8 +28,8 @@ extern "C" {
 /* ABI revision.  2: rgan_adam_packed takes step = device float[2] (step[1] is the
  * call's uint32 arrival ticket, zero before the first call); revision 1 took float[1].
  * 3: adds rgan_conv_wgrad_rows.  4: adds rgan_bn_segment_apply and rgan_bn_backward_sums_apply.
- * rgan_diffaug_workspace, rgan_diffaug and rgan_ema_update are additive within revision 4 (nothing
- * else changed). */
+ * rgan_diffaug_workspace, rgan_diffaug, rgan_ema_update, rgan_diffaug_p, rgan_ada_update and
+ * rgan_ada_adjust are additive within revision 4 (nothing else changed). */
 #define RGAN_ABI_VERSION 4
 
 /* Activation codes fused into epilogues (GLI:345,370,388,417,437,450; SELU GLI:338). */
@@ -509,6 +509,41 @@ int rgan_gather_images(const float* images, const long long* idx, int batch, lon
 size_t rgan_diffaug_workspace(int batch, int channels, int h, int w);
 int rgan_diffaug(const float* x, const float* u, int batch, int channels, int h, int w, int policy,
                  int adjoint, float* ws, float* y, void* stream);
+
+/* ---- the same transform, each group applied with probability p (--rgan_aug_p, --rgan_ada_target) ----
+ * (additive within ABI revision 4: no existing entry point changed)
+ * gate: [batch][4] uniforms in [0, 1); columns 0, 1, 2 gate colour, translation and cutout of
+ * the sample (3 reserved).  p: one device double, read by the kernels at run time, so a call
+ * captured in a HIP graph follows a p written between replays (rgan_ada_update moves it).
+ * Group g of sample b is applied iff policy has its bit and gate[b][g] < (float)*p (strict:
+ * p = 0 opens nothing, p = 1 everything; a NaN p opens nothing).  With m_b = policy restricted to
+ * sample b's open groups, sample b's output equals bit for bit rgan_diffaug's for that sample
+ * alone with policy m_b: the kernels are rgan_diffaug's own, compiled with the gate test, and the
+ * split of the sample sum is unchanged.  So m_b = 0 copies the sample, and a sample whose colour
+ * gate is closed is a pure move (the colour map with identity parameters would round); its
+ * reduction blocks return before loading anything.  Workspace: rgan_diffaug_workspace.
+ * Arguments as rgan_diffaug, plus gate and p non-null. */
+int rgan_diffaug_p(const float* x, const float* u, const float* gate, const double* p, int batch,
+                   int channels, int h, int w, int policy, int adjoint, float* ws, float* y,
+                   void* stream);
+
+/* ---- adaptive augmentation probability (--rgan_ada_target; no reference counterpart) ----
+ * (additive within ABI revision 4: no existing entry point changed)
+ * state = device double[4] {p, S, N, calls}; hyper = device double[4] {target, interval,
+ * images_per_unit_p, reserved}.  Both are read on the device at run time: a captured call keeps
+ * counting across graph replays and follows a hyper-parameter written between them.
+ * rgan_ada_update: the rank statistic of one D step over rows i < n of the two output vectors,
+ *   S += #(y_real[i] > y_fake[i]) - #(y_real[i] < y_fake[i]);  N += n
+ * (a tie or a comparison with a NaN counts 0).  One launch of one block; the integer counts are
+ * added in a fixed order without atomics, and S, N are integers held exactly in double, so shards
+ * of a batch add exactly in any order.  With adjust != 0 the same launch then does what
+ * rgan_ada_adjust does:
+ *   calls += 1;  if (calls mod interval == 0 and N > 0) {
+ *     r = S / N;  p = clamp(p + sgn(r - target) N / images_per_unit_p, 0, 1)  (sgn(0) = 0);  S = N = 0 }
+ * all in double.  Null pointers and n <= 0 are refused (RGAN_EINVAL) without a launch. */
+int rgan_ada_update(const float* y_real, const float* y_fake, int n, const double* hyper,
+                    double* state, int adjust, void* stream);
+int rgan_ada_adjust(const double* hyper, double* state, void* stream);
 
 /* ---- exponential moving average of G's weights (--rgan_ema_G; no reference counterpart) ----
  * (additive within ABI revision 4: no existing entry point changed)

@@ -135,7 +135,10 @@ _SIGS = {
     "rgan_rng_choice": (c_int, [c_vp, c_int, c_int, ctypes.c_ulonglong, c_vp, c_vp]),
     "rgan_diffaug_workspace": (c_sz, [c_int, c_int, c_int, c_int]),
     "rgan_diffaug": (c_int, [c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_int, c_vp, c_vp, c_vp]),
+    "rgan_diffaug_p": (c_int, [c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_int, c_vp, c_vp, c_vp]),
     "rgan_ema_update": (c_int, [c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "rgan_ada_update": (c_int, [c_vp, c_vp, c_int, c_vp, c_vp, c_int, c_vp]),
+    "rgan_ada_adjust": (c_int, [c_vp, c_vp, c_vp]),
     "rgan_set_gemm_emulation": (c_int, [c_int]),
     "rgan_profile_begin": (c_int, [c_int]),
     "rgan_profile_end": (c_int, [c_vp, c_vp, c_vp]),

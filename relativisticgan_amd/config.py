@@ -6,7 +6,9 @@ order, bit-compatible inputs; ``device``: draw on the GPU, for throughput runs) 
 ``--rgan_sync_bn`` (BatchNorm statistics under data parallelism: default off = the
 reference's DataParallel, each rank normalises with its own shard; on = SyncBN over the
 global batch), ``--rgan_diffaug`` (differentiable augmentation of D's inputs, off by
-default; relativisticgan_amd/augment.py), ``--rgan_ema_G BETA`` with ``--rgan_ema_warmup``
+default; relativisticgan_amd/augment.py; its strength: ``--rgan_aug_p P``, each transform applied
+to a sample with probability P, and ``--rgan_ada_target T`` with ``--rgan_ada_interval`` /
+``--rgan_ada_kimg``, P adapted during training, see ``validate_ada``), ``--rgan_ema_G BETA`` with ``--rgan_ema_warmup``
 (an exponential moving average of G's weights, kept next to G, checkpointed, sampled and used
 for the extra images; 0 = off, the default; relativisticgan_amd/ema.py), ``--rgan_r1 GAMMA`` /
 ``--rgan_r2 GAMMA`` with ``--rgan_reg_every K`` (the zero-centred gradient penalties
@@ -81,6 +83,18 @@ def make_parser(script="GAN_losses_iter"):
                    help="differentiable augmentation of every image D sees, reals and fakes, with G's gradient "
                         "flowing back through it: a comma-separated subset of color,translation,cutout "
                         "(default '': off; not with --rgan_pac 2)")
+    p.add_argument("--rgan_aug_p", type=float, default=None,
+                   help="apply each --rgan_diffaug transform to a sample with this probability, in [0, 1]: the "
+                        "fixed value, or with --rgan_ada_target the initial one (default unset: 1 without "
+                        "adaptation, i.e. every transform on every image; 0 with it)")
+    p.add_argument("--rgan_ada_target", type=float, default=0.0,
+                   help="adapt the augmentation probability during training: raise it while r = mean sign(D(x_i) "
+                        "- D(G(z_i))) over the (real, fake) pairs of D's steps exceeds T, lower it while r is "
+                        "below; in (0, 1), e.g. 0.6 (default 0: no adaptation)")
+    p.add_argument("--rgan_ada_interval", type=int, default=4,
+                   help="adjust the probability after every K-th D step (default 4)")
+    p.add_argument("--rgan_ada_kimg", type=float, default=500.0,
+                   help="thousands of images over which the probability may cross from 0 to 1 (default 500)")
     p.add_argument("--rgan_ema_G", type=float, default=0.0,
                    help="keep an exponential moving average of G's weights with this decay, in [0, 1) (e.g. "
                         "0.999): checkpointed as G_ema, sampled next to G's own sample grid and used for the "
@@ -118,9 +132,34 @@ def parse(argv=None):
         parser.error(f"--rgan_ema_G must lie in [0, 1) (0 = off), got {ns.rgan_ema_G}")
     try:
         validate_reg(ns.rgan_r1, ns.rgan_r2, ns.rgan_reg_every, ns.pac)
+        validate_ada(ns.rgan_diffaug, ns.rgan_aug_p, ns.rgan_ada_target, ns.rgan_ada_interval, ns.rgan_ada_kimg)
     except ValueError as e:
         parser.error(str(e))
     return ns
+
+
+ADA_DEFAULTS = (4, 500.0)  # --rgan_ada_interval, --rgan_ada_kimg
+
+
+def validate_ada(policy, aug_p=None, target=0.0, interval=4, kimg=500.0):
+    """Check --rgan_aug_p / --rgan_ada_target / --rgan_ada_interval / --rgan_ada_kimg (ValueError
+    otherwise).  Returns ``(gated, p0)``: whether the transforms are gated at all (unset flags:
+    no, the ungated path as before) and the fixed or initial probability."""
+    target = float(target or 0.0)
+    given = aug_p is not None or target != 0.0 or (interval, float(kimg)) != ADA_DEFAULTS
+    if given and not (policy or "").strip(" ,"):
+        raise ValueError("--rgan_aug_p / --rgan_ada_target / --rgan_ada_interval / --rgan_ada_kimg set the strength "
+                         "of --rgan_diffaug: name the transforms there")
+    if aug_p is not None and not 0.0 <= aug_p <= 1.0:
+        raise ValueError(f"--rgan_aug_p must lie in [0, 1], got {aug_p}")
+    if target != 0.0 and not 0.0 < target < 1.0:
+        raise ValueError(f"--rgan_ada_target must lie in (0, 1) (0 = no adaptation), got {target}")
+    if interval < 1:
+        raise ValueError(f"--rgan_ada_interval must be >= 1, got {interval}")
+    if not kimg > 0:
+        raise ValueError(f"--rgan_ada_kimg must be > 0, got {kimg}")
+    gated = aug_p is not None or target != 0.0
+    return gated, float(aug_p) if aug_p is not None else (0.0 if target != 0.0 else 1.0)
 
 
 def validate_reg(r1, r2, every, pac=1):

@@ -64,14 +64,29 @@ __device__ __forceinline__ AugParam aug_param(const float* __restrict__ u, int b
   return p;
 }
 
+// rgan_diffaug_p: `policy` restricted to the groups sample b's gates open, gate[b][g] < (float)*p
+// (strict; columns 0, 1, 2 = colour, translation, cutout).  Everything downstream sees that
+// mask as the sample's policy, so a closed group takes the same path as a cleared policy bit.
+__device__ __forceinline__ int aug_open(const float* __restrict__ gate, const double* __restrict__ prob, int b,
+                                        int policy) {
+  const float p = (float)prob[0];
+  const float* g = gate + 4LL * b;
+  return policy & ((g[0] < p ? 1 : 0) | (g[1] < p ? 2 : 0) | (g[2] < p ? 4 : 0));
+}
+
 // ws[b][blockIdx.x] = this block's share of the sample sum: of x (forward), or of the dy
 // positions the adjoint scatters back (not cut out, target inside the image).  Block k sums
 // items [k per, (k+1) per) of the sample, each thread its items in order, then block_sum.
-template <int VEC>
+template <int VEC, bool GATED>
 __global__ __launch_bounds__(256) void aug_reduce(const float* __restrict__ in, const float* __restrict__ u, int C,
-                                                  int H, int W, int policy, int adjoint, float* __restrict__ ws) {
+                                                  int H, int W, int policy, int adjoint, float* __restrict__ ws,
+                                                  const float* __restrict__ gate, const double* __restrict__ prob) {
   __shared__ float red[16];
   const int b = blockIdx.y, nblk = gridDim.x;
+  if (GATED) {
+    policy = aug_open(gate, prob, b, policy);
+    if (!(policy & 1)) return;  // whole block (b is per block): aug_apply moves this sample, ws unread
+  }
   const AugParam p = aug_param(u, b, H, W, policy);
   const int items = H * W / VEC;
   const int per = (items + nblk - 1) / nblk;
@@ -110,13 +125,15 @@ __global__ __launch_bounds__(256) void aug_reduce(const float* __restrict__ in, 
 // One item (VEC pixels x C channels) per thread.  `in` is x (forward) or dy (adjoint); the
 // adjoint reads through the opposite shift and tests the cutout box at its SOURCE position
 // (the forward's output position).
-template <int VEC>
+template <int VEC, bool GATED>
 __global__ __launch_bounds__(256) void aug_apply(const float* __restrict__ in, const float* __restrict__ u, int C,
                                                  int H, int W, int policy, int adjoint, int nblk,
-                                                 const float* __restrict__ ws, float* __restrict__ out) {
+                                                 const float* __restrict__ ws, float* __restrict__ out,
+                                                 const float* __restrict__ gate, const double* __restrict__ prob) {
   const int b = blockIdx.y;
   const int q = blockIdx.x * blockDim.x + threadIdx.x;
   if (q >= H * W / VEC) return;
+  if (GATED) policy = aug_open(gate, prob, b, policy);
   const AugParam p = aug_param(u, b, H, W, policy);
   const bool colour = policy & 1;
   const long long plane = (long long)H * W;
@@ -233,25 +250,52 @@ extern "C" size_t rgan_diffaug_workspace(int batch, int channels, int h, int w) 
   return (size_t)batch * (size_t)aug_blocks((long long)h * w);  // the VEC = 1 split: the larger one
 }
 
-extern "C" int rgan_diffaug(const float* x, const float* u, int batch, int channels, int h, int w, int policy,
-                            int adjoint, float* ws, float* y, void* stream) {
+// Both entry points: gate == nullptr runs the ungated instantiations (rgan_diffaug), whose
+// instructions are the ones they were before the gate existed (gate and p are the kernels' last
+// arguments, so even the argument offsets are).
+static int aug_launch(const float* x, const float* u, const float* gate, const double* p, int batch, int channels,
+                      int h, int w, int policy, int adjoint, float* ws, float* y, void* stream) {
   RGAN_REQUIRE(x && u && ws && y && x != y);
   RGAN_REQUIRE(batch > 0 && channels > 0 && h > 0 && w > 0 && policy >= 0 && policy <= 7);
-  RGAN_REQUIRE(batch <= 65535 && (long long)channels * h * w <= INT_MAX);
+  // (two steps: the product of three ints near 2^31 would overflow 64 bits)
+  RGAN_REQUIRE(batch <= 65535 && (long long)channels * h <= INT_MAX && (long long)channels * h * w <= INT_MAX);
   hipStream_t s = (hipStream_t)stream;
   const bool vec = w % 4 == 0 && ((uintptr_t)x | (uintptr_t)y) % 16 == 0;
   const int items = h * w / (vec ? 4 : 1);
   const int nblk = aug_blocks(items);
   adjoint = adjoint != 0;
   if (policy & 1) {
-    if (vec) aug_reduce<4><<<dim3(nblk, batch), 256, 0, s>>>(x, u, channels, h, w, policy, adjoint, ws);
-    else aug_reduce<1><<<dim3(nblk, batch), 256, 0, s>>>(x, u, channels, h, w, policy, adjoint, ws);
+    const dim3 grid(nblk, batch);
+    if (gate) {
+      if (vec) aug_reduce<4, true><<<grid, 256, 0, s>>>(x, u, channels, h, w, policy, adjoint, ws, gate, p);
+      else aug_reduce<1, true><<<grid, 256, 0, s>>>(x, u, channels, h, w, policy, adjoint, ws, gate, p);
+    } else {
+      if (vec) aug_reduce<4, false><<<grid, 256, 0, s>>>(x, u, channels, h, w, policy, adjoint, ws, gate, p);
+      else aug_reduce<1, false><<<grid, 256, 0, s>>>(x, u, channels, h, w, policy, adjoint, ws, gate, p);
+    }
     RGAN_CHECK_LAUNCH();
   }
   const int threads = items >= 4096 ? 256 : 64;  // small images: more, smaller blocks
   const dim3 grid(ceil_div(items, threads), batch);
-  if (vec) aug_apply<4><<<grid, threads, 0, s>>>(x, u, channels, h, w, policy, adjoint, nblk, ws, y);
-  else aug_apply<1><<<grid, threads, 0, s>>>(x, u, channels, h, w, policy, adjoint, nblk, ws, y);
+  if (gate) {
+    if (vec) aug_apply<4, true><<<grid, threads, 0, s>>>(x, u, channels, h, w, policy, adjoint, nblk, ws, y, gate, p);
+    else aug_apply<1, true><<<grid, threads, 0, s>>>(x, u, channels, h, w, policy, adjoint, nblk, ws, y, gate, p);
+  } else {
+    if (vec) aug_apply<4, false><<<grid, threads, 0, s>>>(x, u, channels, h, w, policy, adjoint, nblk, ws, y, gate, p);
+    else aug_apply<1, false><<<grid, threads, 0, s>>>(x, u, channels, h, w, policy, adjoint, nblk, ws, y, gate, p);
+  }
   RGAN_CHECK_LAUNCH();
   return 0;
+}
+
+extern "C" int rgan_diffaug(const float* x, const float* u, int batch, int channels, int h, int w, int policy,
+                            int adjoint, float* ws, float* y, void* stream) {
+  return aug_launch(x, u, nullptr, nullptr, batch, channels, h, w, policy, adjoint, ws, y, stream);
+}
+
+extern "C" int rgan_diffaug_p(const float* x, const float* u, const float* gate, const double* p, int batch,
+                              int channels, int h, int w, int policy, int adjoint, float* ws, float* y,
+                              void* stream) {
+  RGAN_REQUIRE(gate && p);
+  return aug_launch(x, u, gate, p, batch, channels, h, w, policy, adjoint, ws, y, stream);
 }

@@ -1155,17 +1155,28 @@ def gather_images(images, idx, out=None):
 
 
 # ------------------------------------------------------------------ differentiable augmentation
-def diffaug(x, u, policy, adjoint=False, out=None):
+def diffaug(x, u, policy, adjoint=False, out=None, gate=None, p=None):
     """The per-sample colour / translation / cutout transform of include/rgan.h rgan_diffaug
     (``policy``: bit 1 colour, 2 translation, 4 cutout; ``u``: [B][8] uniforms), or with
     ``adjoint`` its transpose applied to a gradient.  ``out``: a contiguous buffer other than
-    ``x`` (e.g. half of a batched D input)."""
+    ``x`` (e.g. half of a batched D input).  With ``gate`` ([B][4] uniforms) and ``p`` (a device
+    double) each group of a sample is applied iff its gate is below p (rgan_diffaug_p)."""
     L.require_cuda(x, u, out)
     if x.dim() != 4 or x.dtype != torch.float32 or u.dtype != torch.float32:
         raise L.RganError("diffaug: x must be a float32 [B][C][H][W] tensor and u float32")
     B, C, H, W = x.shape
     if tuple(u.shape) != (B, 8):
         raise L.RganError(f"diffaug: u must be [{B}][8] (one row of uniforms per sample), got {tuple(u.shape)}")
+    if (gate is None) != (p is None):
+        raise L.RganError("diffaug: gate and p come together (both or neither)")
+    if gate is not None:
+        if not (torch.is_tensor(gate) and torch.is_tensor(p)) or not (gate.is_cuda and p.is_cuda):
+            raise L.RganError("diffaug: gate and p must be device tensors (p is read by the kernel at run time)")
+        if gate.dtype != torch.float32 or tuple(gate.shape) != (B, 4) or not gate.is_contiguous():
+            raise L.RganError(f"diffaug: gate must be a contiguous float32 [{B}][4] tensor, got {gate.dtype} "
+                              f"{tuple(gate.shape)}")
+        if p.dtype != torch.float64 or p.numel() != 1 or gate.device != x.device or p.device != x.device:
+            raise L.RganError("diffaug: p must be one float64 on x's device")
     x = x.contiguous()
     u = u.contiguous()
     if out is None:
@@ -1174,9 +1185,45 @@ def diffaug(x, u, policy, adjoint=False, out=None):
         raise L.RganError("diffaug: out must be contiguous float32 and shaped like x")
     lib = L.lib()
     ws = torch.empty(max(int(lib.rgan_diffaug_workspace(B, C, H, W)), 1), dtype=torch.float32, device=x.device)
+    if gate is not None:
+        L.check(lib.rgan_diffaug_p(L.ptr(x), L.ptr(u), L.ptr(gate), L.ptr(p), B, C, H, W, int(policy),
+                                   int(bool(adjoint)), L.ptr(ws), L.ptr(out), L.stream()), "rgan_diffaug_p")
+        return out
     L.check(lib.rgan_diffaug(L.ptr(x), L.ptr(u), B, C, H, W, int(policy), int(bool(adjoint)), L.ptr(ws), L.ptr(out),
                              L.stream()), "rgan_diffaug")
     return out
+
+
+# ------------------------------------------------------------------ adaptive augmentation probability
+def _ada_arrays(hyper, state):
+    L.require_cuda(hyper, state)
+    for name, t in (("hyper", hyper), ("state", state)):
+        if t.dtype != torch.float64 or t.numel() != 4 or not t.is_contiguous():
+            raise L.RganError(f"ada: {name} must be a contiguous float64[4] device tensor")
+    if hyper.device != state.device:
+        raise L.RganError("ada: hyper and state must share a device")
+
+
+def ada_update(y_real, y_fake, hyper, state, adjust=True):
+    """The rank statistic of one D step added into ``state`` = {p, S, N, calls} (include/rgan.h
+    rgan_ada_update): S += #(y_real > y_fake) - #(y_real < y_fake) row by row, N += rows; with
+    ``adjust`` the controller step of ``ada_adjust`` in the same launch."""
+    _ada_arrays(hyper, state)
+    L.require_cuda(y_real, y_fake)
+    _f32(y_real, y_fake)
+    n = y_real.numel()
+    if n <= 0 or y_fake.numel() != n or y_real.device != state.device or y_fake.device != state.device:
+        raise L.RganError(f"ada_update: y_real and y_fake must hold the same number (> 0) of outputs on the "
+                          f"state's device, got {n} and {y_fake.numel()}")
+    y_real, y_fake = y_real.contiguous(), y_fake.contiguous()
+    L.check(L.lib().rgan_ada_update(L.ptr(y_real), L.ptr(y_fake), n, L.ptr(hyper), L.ptr(state), int(bool(adjust)),
+                                    L.stream()), "rgan_ada_update")
+
+
+def ada_adjust(hyper, state):
+    """calls += 1 and, at every interval-th call with N > 0, the move of p (rgan_ada_adjust)."""
+    _ada_arrays(hyper, state)
+    L.check(L.lib().rgan_ada_adjust(L.ptr(hyper), L.ptr(state), L.stream()), "rgan_ada_adjust")
 
 
 # ------------------------------------------------------------------ moving average of G

@@ -25,6 +25,9 @@ dispatcher-level tracers see the MI355X kernels as graph nodes (not opaque Pytho
   rgan::gp_zc_penalty_backward
   rgan::diffaug          colour / translation / cutout of D's inputs (--rgan_diffaug; not in the reference)
   rgan::diffaug_backward its adjoint
+  rgan::diffaug_p        the same, each group of a sample applied with probability p (--rgan_aug_p, --rgan_ada_target)
+  rgan::diffaug_p_backward
+  rgan::ada_update_      rank statistic of a D step and the controller of p (--rgan_ada_target, mutating)
   rgan::adam_            torch.optim.Adam's single-tensor step (mutating)          GLI:659,712
   rgan::ema_update_      moving average of G's weights (--rgan_ema_G, mutating; not in the reference)
 
@@ -541,6 +544,49 @@ def _(g, u, policy):
 diffaug_backward.register_autograd(_no_double("diffaug_backward"), setup_context=lambda ctx, inputs, output: None)
 
 
+@torch.library.custom_op("rgan::diffaug_p", mutates_args=(), device_types=_DEV)
+def diffaug_p(x: torch.Tensor, u: torch.Tensor, gate: torch.Tensor, p: torch.Tensor, policy: int) -> torch.Tensor:
+    """rgan::diffaug with each group of a sample applied iff its gate (gate [B][4] uniforms) is
+    below p (one device double, read at run time; include/rgan.h rgan_diffaug_p)."""
+    return K.diffaug(x, u, policy, gate=gate, p=p)
+
+
+@diffaug_p.register_fake
+def _(x, u, gate, p, policy):
+    return torch.empty(x.shape, dtype=torch.float32, device=x.device)
+
+
+def _aug_p_setup(ctx, inputs, output):
+    x, u, gate, p, policy = inputs
+    ctx.policy = policy
+    ctx.save_for_backward(u, gate, p)
+
+
+def _aug_p_backward(ctx, g):
+    u, gate, p = ctx.saved_tensors
+    return torch.ops.rgan.diffaug_p_backward(g, u, gate, p, ctx.policy), None, None, None, None
+
+
+diffaug_p.register_autograd(_aug_p_backward, setup_context=_aug_p_setup)
+
+
+@torch.library.custom_op("rgan::diffaug_p_backward", mutates_args=(), device_types=_DEV)
+def diffaug_p_backward(g: torch.Tensor, u: torch.Tensor, gate: torch.Tensor, p: torch.Tensor,
+                       policy: int) -> torch.Tensor:
+    """The gated transform's adjoint applied to g (rgan_diffaug_p with adjoint = 1), under the
+    gates and the p of the forward."""
+    return K.diffaug(g, u, policy, adjoint=True, gate=gate, p=p)
+
+
+@diffaug_p_backward.register_fake
+def _(g, u, gate, p, policy):
+    return torch.empty(g.shape, dtype=torch.float32, device=g.device)
+
+
+diffaug_p_backward.register_autograd(_no_double("diffaug_p_backward"),
+                                     setup_context=lambda ctx, inputs, output: None)
+
+
 # ------------------------------------------------------------------ optimizer
 @torch.library.custom_op("rgan::adam_", mutates_args=("params", "exp_avgs", "exp_avg_sqs", "step"),
                          device_types=_DEV)
@@ -567,6 +613,21 @@ def ema_update_(avgs: List[torch.Tensor], params: List[torch.Tensor], hyper: tor
 
 @ema_update_.register_fake
 def _(avgs, params, hyper, count):
+    return None
+
+
+# ------------------------------------------------------------------ adaptive augmentation probability
+@torch.library.custom_op("rgan::ada_update_", mutates_args=("state",), device_types=_DEV)
+def ada_update_(y_real: torch.Tensor, y_fake: torch.Tensor, hyper: torch.Tensor, state: torch.Tensor,
+                adjust: bool) -> None:
+    """One D step's rank statistic added into state = double[4] {p, S, N, calls}, and with
+    ``adjust`` the controller step (hyper = double[4] {target, interval, images_per_unit_p, 0};
+    include/rgan.h rgan_ada_update)."""
+    K.ada_update(y_real, y_fake, hyper, state, adjust)
+
+
+@ada_update_.register_fake
+def _(y_real, y_fake, hyper, state, adjust):
     return None
 
 
@@ -602,4 +663,4 @@ def layer_forward(layer, h, training):
 OPS = ("conv2d", "conv2d_dgrad", "conv2d_wgrad", "channel_sum", "act_backward", "batch_norm_stats_",
        "batch_norm_apply", "batch_norm_backward", "spectral_power_", "spectral_scale", "spectral_backward", "loss_head",
        "loss_head_grad", "gp_penalty", "gp_penalty_backward", "gp_zc_penalty", "gp_zc_penalty_backward", "diffaug",
-       "diffaug_backward", "adam_", "ema_update_")
+       "diffaug_backward", "diffaug_p", "diffaug_p_backward", "adam_", "ema_update_", "ada_update_")

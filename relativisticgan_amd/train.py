@@ -13,7 +13,11 @@ scope), the same log line (GLI:723) and the same checkpoint dict (GLI:737-747). 
 optimizer step, is checkpointed under one more key, ``G_ema``, and draws a second sample grid.
 With ``--rgan_r1`` / ``--rgan_r2`` the D step ends with the zero-centred gradient penalties on
 the real / generated batch D saw (after errD and the WGAN-GP penalty), in the iterations
-``--rgan_reg_every`` names (config.reg_weight).
+``--rgan_reg_every`` names (config.reg_weight).  With ``--rgan_aug_p`` / ``--rgan_ada_target`` the
+transforms of ``--rgan_diffaug`` are gated per sample with a probability p (one more draw, the
+gates, after each draw of the transforms' uniforms); under adaptation every D step's outputs move
+p (augment.AdaptiveP), the log line ends with ``ada_p: ... r: ...`` and checkpoints gain the
+key ``ada``.
 """
 import os
 import random
@@ -24,7 +28,7 @@ import numpy
 import torch
 
 from . import augment, autograd, dp
-from .config import TITLES, parse, reg_weight, validate_reg
+from .config import TITLES, parse, reg_weight, validate_ada, validate_reg
 from .ema import GeneratorEMA
 from .kernels import DeviceRNG
 from .losses import (gradient_penalty, loss_D, loss_D_cat, loss_D_fake, loss_D_real, loss_G, loss_G_cat, unit_seed,
@@ -109,6 +113,12 @@ class Trainer:
         self.pac = getattr(p, "pac", 1)  # 2: code/GAN_losses_iter_PAC.py
         # --rgan_diffaug: the kernel's policy mask (0 = off: no call, no draw)
         self.aug = augment.validate(getattr(p, "rgan_diffaug", ""), self.pac)
+        # --rgan_aug_p / --rgan_ada_target: the transforms gated per sample with a probability kept
+        # (and under adaptation moved) on the device (None = off: the ungated call, no gate draw)
+        ada = (getattr(p, "rgan_ada_target", 0.0) or 0.0, getattr(p, "rgan_ada_interval", 4),
+               getattr(p, "rgan_ada_kimg", 500.0))
+        gated, p0 = validate_ada(getattr(p, "rgan_diffaug", ""), getattr(p, "rgan_aug_p", None), *ada)
+        self.ada = augment.AdaptiveP(self.device, p0, *ada) if gated else None
         # --rgan_r1 / --rgan_r2 / --rgan_reg_every: the zero-centred penalties' gammas and their
         # lazy period (0 = off: no extra D call, nothing launched)
         self.r1 = float(getattr(p, "rgan_r1", 0.0) or 0.0)
@@ -187,24 +197,40 @@ class Trainer:
     def _aug_u(self, feed, key, groups):
         """This rank's [groups*B][8] augmentation uniforms: one draw of groups * batch_size rows
         for the global batch (group k = rows [k*batch_size, (k+1)*batch_size)), each group
-        sharded like ``_uniform``."""
-        if feed is not None and key in feed:
-            return feed[key]
+        sharded like ``_uniform``.  With gating on, the [groups*B][4] gates come with them
+        (feed key ``gate_D`` / ``gate_G``), drawn directly after from the same generator and
+        sharded the same way; None otherwise."""
         n = self.p.batch_size
-        u = augment.draw(groups * n, self.host_rng, self.dev_rng)
-        if self.world > 1:
-            u = torch.cat([self._shard(u[k * n:(k + 1) * n]) for k in range(groups)])
-        return u.to(self.device, non_blocking=True)
 
-    def _augment_pair(self, a, b, u, raw, out):
+        def rows(key, draw):
+            if feed is not None and key in feed:
+                return feed[key]
+            t = draw(groups * n, self.host_rng, self.dev_rng)
+            if self.world > 1:
+                t = torch.cat([self._shard(t[k * n:(k + 1) * n]) for k in range(groups)])
+            return t.to(self.device, non_blocking=True)
+
+        u = rows(key, augment.draw)
+        return u, (rows("gate" + key[3:], augment.draw_gates) if self.ada is not None else None)
+
+    def _augment(self, x, u, gate, rows=None, out=None):
+        """T(x) with the given rows of u (and of the gates, under the current p, when gating is on)."""
+        if rows is not None:
+            u, gate = u[rows], (None if gate is None else gate[rows])
+        if gate is None:
+            return augment.apply(x, u, self.aug, out=out)
+        return augment.apply(x, u, self.aug, out=out, gate=gate, p=self.ada.p)
+
+    def _augment_pair(self, a, b, u, gate, raw, out):
         """T(a), T(b) with u's two row groups, written back to back into ``out``: one call over
         both when a and b already lie back to back in ``raw``.  a may carry autograd."""
         B = self.B
         if (raw is not None and not a.requires_grad and a.data_ptr() == raw.data_ptr()
                 and b.data_ptr() == raw[B:].data_ptr()):
-            augment.apply(raw, u, self.aug, out=out)
+            self._augment(raw, u, gate, out=out)
             return out[:B], out[B:]
-        return augment.apply(a, u[:B], self.aug, out=out[:B]), augment.apply(b, u[B:], self.aug, out=out[B:])
+        return (self._augment(a, u, gate, slice(0, B), out=out[:B]),
+                self._augment(b, u, gate, slice(B, None), out=out[B:]))
 
     def _generate_D(self, z, out=None):
         """The D step's fake batch.  Single samples: G(z) without a graph (GLI copies it into
@@ -262,13 +288,13 @@ class Trainer:
             # the pair D reads (same layout); x_raw is the untransformed batch of the record
             raw = torch.empty_like(pair) if pair is not None and self.aug else pair
             x = x_raw = self._real(feed, "x_D", out=raw[:self.B] if raw is not None else None)
-            z = u_aug = None
+            z = u_aug = gate = None
             if self.aug and not self.batch_D:
                 # the separate passes run D(x) before G(z): draw z now, so the draws come in the
                 # batched path's order (x, z, augmentation) whichever path runs
                 z = self._normal(feed, "z_D", zshape)
-                u_aug = self._aug_u(feed, "aug_D", 2)
-                x = augment.apply(x, u_aug[:self.B], self.aug)
+                u_aug, gate = self._aug_u(feed, "aug_D", 2)
+                x = self._augment(x, u_aug, gate, slice(0, self.B))
             if self.batch_D:
                 # D(x) and D(x_fake) as one batched pass (per-call BN statistics kept):
                 # the draws keep the reference's order (x, then z); D(x) does not read G
@@ -276,8 +302,8 @@ class Trainer:
                 self.flush()
                 x_fake = self._generate_D(z, out=raw[self.B:] if raw is not None else None)
                 if self.aug:
-                    u_aug = self._aug_u(feed, "aug_D", 2)
-                    x, x_fake = self._augment_pair(x, x_fake, u_aug, raw, pair)
+                    u_aug, gate = self._aug_u(feed, "aug_D", 2)
+                    x, x_fake = self._augment_pair(x, x_fake, u_aug, gate, raw, pair)
                 laid_out = (pair is not None and x.data_ptr() == pair.data_ptr()
                             and x_fake.data_ptr() == pair[self.B:].data_ptr())
                 y_all = D.forward_pair(x, x_fake, cat=pair if laid_out else None)
@@ -298,7 +324,7 @@ class Trainer:
                 self.flush()
                 x_fake = self._generate_D(z)
                 if self.aug:
-                    x_fake = augment.apply(x_fake, u_aug[self.B:], self.aug)
+                    x_fake = self._augment(x_fake, u_aug, gate, slice(self.B, None))
                 y_pred_fake = D(x_fake)
                 err_fake = loss_D_fake(kind, y_pred_fake)
                 if last_bwd == "errD":
@@ -312,7 +338,7 @@ class Trainer:
                 self.flush()
                 x_fake = self._generate_D(z)
                 if self.aug:
-                    x_fake = augment.apply(x_fake, u_aug[self.B:], self.aug)
+                    x_fake = self._augment(x_fake, u_aug, gate, slice(self.B, None))
                 y_pred_fake = D(x_fake)
                 errD = loss_D(kind, y_pred, y_pred_fake)
                 if last_bwd == "errD":
@@ -322,6 +348,9 @@ class Trainer:
                    "errD": errD.detach()}
             if self.aug:
                 rec.update(aug=u_aug, x_aug=x, x_fake_aug=x_fake)
+            if self.ada is not None:
+                rec.update(gate=gate)
+                self.ada.update(rec["y_pred"], rec["y_pred_fake"])  # (nothing without --rgan_ada_target)
             if gp_on:
                 # with augmentation on, x and x_fake are the transformed batches: what D saw
                 u = self._uniform(feed, "u", (p.batch_size, 1, 1, 1))
@@ -376,8 +405,8 @@ class Trainer:
                 x = x_raw = self._real(feed, "x_G", out=None if self.aug else pair_G[self.B:])
                 if self.aug:
                     # T(G(z)) carries autograd back into G; fake first, then real (the BN call order)
-                    u_aug = self._aug_u(feed, "aug_G", 2)
-                    fake, x = self._augment_pair(fake, x, u_aug, None, pair_G)
+                    u_aug, gate = self._aug_u(feed, "aug_G", 2)
+                    fake, x = self._augment_pair(fake, x, u_aug, gate, None, pair_G)
                     recG.update(aug=u_aug)
                 laid_out = (fake.data_ptr() == pair_G.data_ptr()
                             and x.data_ptr() == pair_G[self.B:].data_ptr())
@@ -391,8 +420,8 @@ class Trainer:
                     # the draws keep the batched path's order: z, the real batch, augmentation
                     if kind > 4:
                         x = self._real(feed, "x_G")
-                    u_aug = self._aug_u(feed, "aug_G", 2 if kind > 4 else 1)
-                    fake = augment.apply(fake, u_aug[:self.B], self.aug)
+                    u_aug, gate = self._aug_u(feed, "aug_G", 2 if kind > 4 else 1)
+                    fake = self._augment(fake, u_aug, gate, slice(0, self.B))
                     recG.update(aug=u_aug)
                 y_pred_fake = D(fake)
                 y_pred = None
@@ -400,9 +429,11 @@ class Trainer:
                     if x is None:
                         x = self._real(feed, "x_G")
                     with torch.no_grad():
-                        y_pred = D(augment.apply(x, u_aug[self.B:], self.aug) if self.aug else x)
+                        y_pred = D(self._augment(x, u_aug, gate, slice(self.B, None)) if self.aug else x)
                     recG.update(x=x, y_pred=y_pred)
                 errG = loss_G(kind, y_pred_fake, y_pred)
+            if self.ada is not None:
+                recG.update(gate=gate)
             self._arm(self.redG)
             self._backward(errG)
             recG.update(y_pred_fake=y_pred_fake.detach(), errG=errG.detach())
@@ -455,6 +486,8 @@ class Trainer:
               "D_scheduler": self.decayD.state_dict(), "z_test": _gather_batch(self.z_test)}
         if self.ema is not None:  # (off: exactly the reference's keys)
             st["G_ema"] = self.ema.state_dict()
+        if self.ada is not None:  # (collective under DP: the pair counts of every rank)
+            st["ada"] = self.ada.state_dict()
         return st
 
     def load(self, ckpt):
@@ -470,6 +503,11 @@ class Trainer:
                 self.ema.load_state_dict(ckpt["G_ema"])
             else:  # written by the reference or with the flag off: average from the loaded G on
                 self.ema.restart()
+        if self.ada is not None:
+            if "ada" in ckpt:
+                self.ada.load_state_dict(ckpt["ada"])
+            else:  # written by the reference or with the flags off: start as the flags say
+                self.ada.restart()
         self.z_test.copy_(self._shard(ckpt["z_test"].to(self.device)) if ckpt["z_test"].shape[0] != self.B
                           else ckpt["z_test"])
         return ckpt["i"], ckpt["current_set_images"]
@@ -477,7 +515,10 @@ class Trainer:
     def log_line(self, i, elapsed):
         """GLI:723."""
         d, g = self.errD.item(), self.errG.item()
-        return '[%d] Diff: %.4f loss_D: %.4f loss_G: %.4f time:%.4f' % (i, -d + g, d, g, elapsed)
+        line = '[%d] Diff: %.4f loss_D: %.4f loss_G: %.4f time:%.4f' % (i, -d + g, d, g, elapsed)
+        if self.ada is not None:
+            line += ' ada_p: %.4f r: %.4f' % self.ada.read()
+        return line
 
 
 def _gather_batch(t):
