@@ -592,7 +592,26 @@ const char* rgan_version(void);
  * on the stream by the numbers it used (graph-replay safe).
  * rgan_rng_fill: out[0..n) ~ N(0, 1) (kind 0, Box-Muller) or U[0, 1) (kind 1).
  * rgan_rng_choice: n <= 4096 distinct indices of [0, N) (numpy.random.choice(N, n,
- * replace=False)'s distribution; Floyd's algorithm on one wave), int64. */
+ * replace=False)'s distribution; Floyd's algorithm on one wave), int64.
+ *
+ * The stream (pinned bit for bit by tests/test_rng_gpu.py against tests/rng_ref.py): counter
+ * value c yields the four 32-bit words w0..w3 = Philox-4x32-10(counter words (c lo, c hi, 0, 0),
+ * key (seed lo, seed hi)); c runs modulo 2^64.
+ *   fill, with base = *counter at the call: element 4q+i comes from counter base+q.
+ *     kind 1: out[4q+i] = (w_i >> 8) 2^-24, a multiple of 2^-24 in [0, 1 - 2^-24]: never 1.
+ *     kind 0: with U(w) = ((w >> 8) + 1) 2^-24 in (0, 1] (the logarithm never sees 0):
+ *             out[4q] = r0 cos(2 pi U(w1)), out[4q+1] = r0 sin(2 pi U(w1)), r0 = sqrt(-2 ln U(w0));
+ *             out[4q+2], out[4q+3] the same with w2 for the radius and w3 for the angle.
+ *             |out| <= sqrt(48 ln 2) ~ 5.768 (U = 2^-24); U = 1 gives a pair of zeros.
+ *     The call advances *counter by ceil(n / 4); a tail (n % 4 != 0) drops the last quad's
+ *     unused elements.
+ *   choice, with base = *counter: an integer below m from one counter's words is
+ *     (((w1 << 32) | w0) m) >> 64.  Floyd: step s = 0..n-1 has j = N-n+s and t below j+1 from
+ *     counter base+s; it picks t, or j if t is already picked.  Then a Fisher-Yates pass over the
+ *     picks: for s = n-1 .. 1 swap positions s and k, k below s+1 from counter base+n+s.
+ *     The call advances *counter by 2 n.
+ * A refused call (RGAN_EINVAL: a null pointer, n < 0, kind other than 0 / 1, N <= 0, n > N,
+ * n > 4096) and n = 0 (returns 0) launch nothing, write nothing and leave *counter unchanged. */
 int rgan_rng_fill(float* out, long long n, int kind, unsigned long long seed, unsigned long long* counter,
                   void* stream);
 int rgan_rng_choice(long long* out, int N, int n, unsigned long long seed, unsigned long long* counter,
