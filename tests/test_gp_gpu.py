@@ -22,6 +22,7 @@ CASES = {
     "arch0_nobn": dict(loss_D=3, image_size=32, D_h_size=8, no_batch_norm_D="True"),
     "arch0_sigmoid_end": dict(loss_D=1, image_size=32, D_h_size=8, grad_penalty="True"),
     "arch1": dict(loss_D=3, image_size=32, arch=1),
+    "arch1_spectral": dict(loss_D=3, image_size=32, arch=1, spectral="True"),
 }
 
 

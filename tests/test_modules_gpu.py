@@ -28,6 +28,12 @@ CASES = [
     dict(arch=0, image_size=32, batch_size=8, z_size=16, G_h_size=8, D_h_size=8, loss_D=7, SELU=True),
     dict(arch=1, image_size=32, batch_size=8, z_size=16, loss_D=8),
     dict(arch=1, image_size=32, batch_size=8, z_size=16, loss_D=1, no_batch_norm_D=True),
+    # spectral norm in G (ConvTranspose2d: dim 1), with NN_conv (3x3 convs: the scalar view), and
+    # arch 1 with it in both nets (3x3 and 4x4, the narrow first layer, the biased 64 -> 3 end conv)
+    dict(arch=0, image_size=32, batch_size=8, z_size=16, G_h_size=8, D_h_size=8, loss_D=7, spectral_G=True),
+    dict(arch=0, image_size=32, batch_size=8, z_size=16, G_h_size=8, D_h_size=8, loss_D=7, NN_conv=True,
+         spectral_G=True),
+    dict(arch=1, image_size=32, batch_size=8, z_size=16, loss_D=8, spectral=True, spectral_G=True),
 ]
 
 
@@ -116,10 +122,16 @@ def test_nets_vs_fp64_torch(case):
         if n in skipg:
             continue
         env(f"G grad {n}", q.grad, q32.grad, q64.grad)
-    # BN running statistics after the train-mode forwards
-    for (n, b), (_, b32), (_, b64) in zip(D.named_buffers(), Do32.named_buffers(), Do64.named_buffers()):
-        if "running" in n:
-            env(n, b, b32, b64, 1e-5)
+    # BN running statistics and spectral u, v after the train-mode forwards, of D and of G
+    for tag, net, o32, o64 in (("D", D, Do32, Do64), ("G", G, Go32, Go64)):
+        d32, d64 = dict(o32.named_buffers()), dict(o64.named_buffers())
+        assert sorted(d64) == sorted(n for n, _ in net.named_buffers())
+        for n, b in net.named_buffers():
+            b32, b64 = d32[n], d64[n]
+            if "running" in n or n.endswith(("weight_u", "weight_v")):
+                env(f"{tag} {n}", b, b32, b64, 1e-5)
+        spectral = case.get("spectral" if tag == "D" else "spectral_G", False)
+        assert any(n.endswith("weight_u") for n, _ in net.named_buffers()) == bool(spectral)
 
 
 def test_weight_hooks_fire_in_trainer_backward():
