@@ -28,8 +28,9 @@ extern "C" {
 /* ABI revision.  2: rgan_adam_packed takes step = device float[2] (step[1] is the
  * call's uint32 arrival ticket, zero before the first call); revision 1 took float[1].
  * 3: adds rgan_conv_wgrad_rows.  4: adds rgan_bn_segment_apply and rgan_bn_backward_sums_apply.
- * rgan_diffaug_workspace, rgan_diffaug, rgan_ema_update, rgan_diffaug_p, rgan_ada_update and
- * rgan_ada_adjust are additive within revision 4 (nothing else changed). */
+ * rgan_diffaug_workspace, rgan_diffaug, rgan_ema_update, rgan_diffaug_p, rgan_ada_update,
+ * rgan_ada_adjust, rgan_lecam and rgan_lecam_finish are additive within revision 4 (nothing else
+ * changed). */
 #define RGAN_ABI_VERSION 4
 
 /* Activation codes fused into epilogues (GLI:345,370,388,417,437,450; SELU GLI:338). */
@@ -544,6 +545,37 @@ int rgan_diffaug_p(const float* x, const float* u, const float* gate, const doub
 int rgan_ada_update(const float* y_real, const float* y_fake, int n, const double* hyper,
                     double* state, int adjust, void* stream);
 int rgan_ada_adjust(const double* hyper, double* state, void* stream);
+
+/* ---- LeCam regularisation of D (--rgan_lecam; Tseng et al., CVPR 2021; no reference counterpart) ----
+ * (additive within ABI revision 4: no existing entry point changed)
+ * state = device double[4] {a_real, a_fake, calls, 0}; hyper = device double[4] {lambda, beta, start,
+ * reserved}.  Both are read on the device at run time: a captured call keeps moving the anchors
+ * across graph replays and follows a hyper-parameter written between them.
+ * rgan_lecam, over rows i < n of D's outputs on this rank's real and generated batch (n_global = the
+ * rows of all ranks, n on one rank; N below):
+ *   w = calls >= start ? lambda : 0                                  (calls as the call finds it)
+ *   L = w [ (1/N) sum (y_real[i] - a_fake)^2 + (1/N) sum (y_fake[i] - a_real)^2 ]
+ *   dy_real[i] = (float)(2 w / N (y_real[i] - a_fake));  dy_fake[i] = (float)(2 w / N (y_fake[i] - a_real))
+ * (the anchors are constants of the call; w == 0: L and both gradients are exact zeros, the launch
+ * is the same).  mode 0 then moves the anchors on the batch means m_r = sum y_real / N, m_f =
+ * sum y_fake / N and writes out[0] = L, out[1..3] = 0:
+ *   calls == 0: a_real = m_r, a_fake = m_f;  else a = beta a + (1 - beta) m;   calls += 1
+ * mode 1 (data parallel) leaves state alone and writes out = {sum y_real, sum y_fake,
+ * sum (y_real - a_fake)^2, sum (y_fake - a_real)^2} of this rank's rows; the caller adds the ranks'
+ * sums and rgan_lecam_finish forms L (into loss[0], which may be sums) and moves the anchors as
+ * mode 0 does.  Either side may be absent (null y, and then a null dy): its part of L, its gradient
+ * and the move of its own anchor (a_real for y_real) are left out, and calls += 1 goes with the
+ * fake side, so a real-only call followed by a fake-only call counts one step (sides of
+ * rgan_lecam_finish: 1 real, 2 fake, 3 both).  A dy may be null (no gradient wanted).  y and dy need
+ * 4-byte alignment only.  All sums and the anchor arithmetic are double, one block adds in a fixed
+ * order without atomics (two calls on the same inputs give the same bits), and a gradient element
+ * is rounded once, from double to fp32.  Refused (RGAN_EINVAL) without a launch: n <= 0,
+ * n_global < n, both y null, a dy given for an absent side, null hyper / state / out / sums / loss,
+ * a mode other than 0 / 1, sides outside 1..3. */
+int rgan_lecam(const float* y_real, const float* y_fake, int n, int n_global, const double* hyper,
+               double* state, float* dy_real, float* dy_fake, double* out, int mode, void* stream);
+int rgan_lecam_finish(const double* sums, int n_global, int sides, const double* hyper,
+                      double* state, double* loss, void* stream);
 
 /* ---- exponential moving average of G's weights (--rgan_ema_G; no reference counterpart) ----
  * (additive within ABI revision 4: no existing entry point changed)

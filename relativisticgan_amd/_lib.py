@@ -139,6 +139,8 @@ _SIGS = {
     "rgan_ema_update": (c_int, [c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "rgan_ada_update": (c_int, [c_vp, c_vp, c_int, c_vp, c_vp, c_int, c_vp]),
     "rgan_ada_adjust": (c_int, [c_vp, c_vp, c_vp]),
+    "rgan_lecam": (c_int, [c_vp, c_vp, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_vp]),
+    "rgan_lecam_finish": (c_int, [c_vp, c_int, c_int, c_vp, c_vp, c_vp, c_vp]),
     "rgan_set_gemm_emulation": (c_int, [c_int]),
     "rgan_profile_begin": (c_int, [c_int]),
     "rgan_profile_end": (c_int, [c_vp, c_vp, c_vp]),

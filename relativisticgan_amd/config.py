@@ -14,7 +14,10 @@ for the extra images; 0 = off, the default; relativisticgan_amd/ema.py), ``--rga
 ``--rgan_r2 GAMMA`` with ``--rgan_reg_every K`` (the zero-centred gradient penalties
 GAMMA / 2 * mean ||dD/dx||^2 on the real / on the generated batch D saw, added to the D step
 after errD and the WGAN-GP penalty; lazily every K-th iteration with weight GAMMA * K, see
-``reg_weight``; 0 = off, the default; not with --rgan_pac 2), ``--rgan_pac 2``
+``reg_weight``; 0 = off, the default; not with --rgan_pac 2), ``--rgan_lecam LAMBDA``
+with ``--rgan_lecam_beta`` / ``--rgan_lecam_start`` (LeCam regularisation: LAMBDA times the squared
+distance of D's outputs from moving averages of its outputs on the other kind of batch, added to
+the D step without another pass of D; 0 = off, the default; see ``validate_lecam``), ``--rgan_pac 2``
 (the PacGAN-2 script, code/GAN_losses_iter_PAC.py, which shares this CLI) and
 ``--rgan_script`` (the defaults of GAN_losses_iter / GAN_losses_iter_art / GAN_losses_iter_PAC).
 """
@@ -51,6 +54,9 @@ ART_DEFAULTS = {
     "CIFAR10_input_folder": "/home/ubuntu/datasets/CIFAR10",
 }
 SCRIPTS = ("GAN_losses_iter", "GAN_losses_iter_art", "GAN_losses_iter_PAC")
+
+
+LECAM_DEFAULTS = (0.99, 1)  # --rgan_lecam_beta, --rgan_lecam_start
 
 
 def make_parser(script="GAN_losses_iter"):
@@ -109,6 +115,16 @@ def make_parser(script="GAN_losses_iter"):
     p.add_argument("--rgan_reg_every", type=int, default=1,
                    help="lazy regularisation: run R1 / R2 in every K-th iteration only (i %% K == 0), with "
                         "weight GAMMA * K (default 1: every iteration)")
+    p.add_argument("--rgan_lecam", type=float, default=0.0,
+                   help="LeCam regularisation of D (Tseng et al., CVPR 2021): add LAMBDA * (mean (D(x) - a_fake)^2 "
+                        "+ mean (D(x_fake) - a_real)^2) to the D step, a_real / a_fake being moving averages of "
+                        "D's outputs on the real / generated batches; meant to go with --rgan_diffaug; e.g. 0.3, "
+                        "the paper's CIFAR value (default 0: off)")
+    p.add_argument("--rgan_lecam_beta", type=float, default=LECAM_DEFAULTS[0],
+                   help="decay of the LeCam anchors' moving averages, in [0, 1) (default 0.99)")
+    p.add_argument("--rgan_lecam_start", type=int, default=LECAM_DEFAULTS[1],
+                   help="the D-step count from which the LeCam term has weight (the anchors move from the first "
+                        "step on); >= 1 (default 1)")
     p.add_argument("--rgan_perf_log", type="bool", default=True,
                    help="after each reference log line, a line with img/s and MFMA%% of the training "
                         "iterations since the previous one (sample PNGs, checkpoints and extra images excluded)")
@@ -133,6 +149,7 @@ def parse(argv=None):
     try:
         validate_reg(ns.rgan_r1, ns.rgan_r2, ns.rgan_reg_every, ns.pac)
         validate_ada(ns.rgan_diffaug, ns.rgan_aug_p, ns.rgan_ada_target, ns.rgan_ada_interval, ns.rgan_ada_kimg)
+        validate_lecam(ns.rgan_lecam, ns.rgan_lecam_beta, ns.rgan_lecam_start)
     except ValueError as e:
         parser.error(str(e))
     return ns
@@ -173,6 +190,21 @@ def validate_reg(r1, r2, every, pac=1):
         raise ValueError("--rgan_reg_every > 1 needs --rgan_r1 or --rgan_r2: it schedules those penalties only")
     if (r1 > 0 or r2 > 0) and pac != 1:
         raise ValueError("--rgan_r1 / --rgan_r2 are not available with --rgan_pac 2")
+
+
+def validate_lecam(lam, beta=LECAM_DEFAULTS[0], start=LECAM_DEFAULTS[1]):
+    """Check --rgan_lecam / --rgan_lecam_beta / --rgan_lecam_start (ValueError otherwise).
+    Returns whether the term is on."""
+    lam = 0.0 if lam is None else lam
+    if not lam >= 0.0:
+        raise ValueError(f"--rgan_lecam must be >= 0 (0 = off), got {lam}")
+    if not 0.0 <= beta < 1.0:
+        raise ValueError(f"--rgan_lecam_beta must lie in [0, 1), got {beta}")
+    if start != int(start) or start < 1:
+        raise ValueError(f"--rgan_lecam_start must be an integer >= 1, got {start}")
+    if lam == 0 and (float(beta), int(start)) != LECAM_DEFAULTS:
+        raise ValueError("--rgan_lecam_beta / --rgan_lecam_start need --rgan_lecam: they shape that term only")
+    return lam > 0
 
 
 def reg_weight(i, every, gamma):

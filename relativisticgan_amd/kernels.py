@@ -1226,6 +1226,67 @@ def ada_adjust(hyper, state):
     L.check(L.lib().rgan_ada_adjust(L.ptr(hyper), L.ptr(state), L.stream()), "rgan_ada_adjust")
 
 
+# ------------------------------------------------------------------ LeCam regularisation of D
+def _lecam_arrays(what, hyper, state, *more):
+    L.require_cuda(hyper, state, *more)
+    for name, t in (("hyper", hyper), ("state", state)) + tuple((f"double[4] #{k}", t) for k, t in enumerate(more)):
+        if t.dtype != torch.float64 or t.numel() != 4 or not t.is_contiguous():
+            raise L.RganError(f"{what}: {name} must be a contiguous float64[4] device tensor")
+        if t.device != state.device:
+            raise L.RganError(f"{what}: {name} must be on the state's device")
+
+
+def lecam(y_real, y_fake, hyper, state, n_global=None, partial=False, need_dr=True, need_df=True, dr=None, df=None,
+          out=None):
+    """The LeCam term of one D step (include/rgan.h rgan_lecam) on D's outputs ``y_real`` /
+    ``y_fake`` (either may be None): returns ``(out, dr, df)``.  Fused (default): ``out[0]`` is the
+    term and ``state`` = {a_real, a_fake, calls, 0} has moved.  ``partial``: ``state`` is left
+    alone and ``out`` holds this rank's four sums for ``lecam_finish``.  The gradients are scaled
+    with ``n_global`` rows (default: this call's).  ``dr`` / ``df``: buffers to write them into
+    (e.g. the halves of one [2B] buffer); ``need_*`` False: that gradient is not formed."""
+    _lecam_arrays("lecam", hyper, state, *(() if out is None else (out,)))
+    if y_real is None and y_fake is None:
+        raise L.RganError("lecam: y_real or y_fake (or both) must be given")
+    t = y_real if y_real is not None else y_fake
+    n = t.numel()
+    n_global = n if n_global is None else int(n_global)
+    if not 1 <= n <= n_global < 2 ** 31:
+        raise L.RganError(f"lecam: n = {n} rows of n_global = {n_global} (need 1 <= n <= n_global < 2^31)")
+    for name, y, d in (("real", y_real, dr), ("fake", y_fake, df)):
+        if y is None and d is not None:
+            raise L.RganError(f"lecam: a gradient buffer for the absent {name} side")
+        for what, v in (("y_" + name, y), ("dy_" + name, d)):
+            if v is None:
+                continue
+            L.require_cuda(v)
+            if v.dtype != torch.float32 or not v.is_contiguous() or v.device != state.device:
+                raise L.RganError(f"lecam: {what} must be a contiguous float32 tensor on the state's device")
+            if v.numel() != n:
+                raise L.RganError(f"lecam: {what} has {v.numel()} elements, expected {n}")
+    if dr is None and y_real is not None and need_dr:
+        dr = torch.empty_like(y_real)
+    if df is None and y_fake is not None and need_df:
+        df = torch.empty_like(y_fake)
+    if out is None:
+        out = torch.empty(4, dtype=torch.float64, device=state.device)
+    L.check(L.lib().rgan_lecam(L.ptr(y_real), L.ptr(y_fake), n, n_global, L.ptr(hyper), L.ptr(state), L.ptr(dr),
+                               L.ptr(df), L.ptr(out), int(bool(partial)), L.stream()), "rgan_lecam")
+    return out, dr, df
+
+
+def lecam_finish(sums, n_global, sides, hyper, state, loss=None):
+    """The all-reduced sums of ``lecam(partial=True)`` turned into the term (returned, a
+    float64[4] whose first element it is) and the move of the anchors (rgan_lecam_finish).
+    ``sides``: 1 the real side was given, 2 the fake side, 3 both."""
+    loss = sums if loss is None else loss
+    _lecam_arrays("lecam_finish", hyper, state, sums, loss)
+    if not 1 <= int(n_global) < 2 ** 31 or int(sides) not in (1, 2, 3):
+        raise L.RganError(f"lecam_finish: n_global = {n_global}, sides = {sides} (need n_global >= 1, sides in 1..3)")
+    L.check(L.lib().rgan_lecam_finish(L.ptr(sums), int(n_global), int(sides), L.ptr(hyper), L.ptr(state), L.ptr(loss),
+                                      L.stream()), "rgan_lecam_finish")
+    return loss
+
+
 # ------------------------------------------------------------------ moving average of G
 def ema_update(avgs, params, hyper, count):
     """One moving-average step of include/rgan.h rgan_ema_update over the tensor pairs:

@@ -1,5 +1,5 @@
-"""The eight --loss_D heads, the WGAN-GP penalty and the zero-centred R1 / R2 penalties as
-autograd ops on the HIP kernels.
+"""The eight --loss_D heads, the WGAN-GP penalty, the zero-centred R1 / R2 penalties and the
+LeCam term (--rgan_lecam) as autograd ops on the HIP kernels.
 
 Heads (GLI:481-484 criteria; D side GLI:592-644; G side GLI:686-709):
   1 SGAN (BCE on D's sigmoid), 2 LSGAN, 3 WGAN(-GP), 4 HingeGAN: real and fake terms
@@ -200,6 +200,78 @@ def loss_G(kind, y_pred_fake, y_pred=None):
     if kind <= 4:
         return _Head.apply(None, _flat(y_pred_fake), kind, 2)
     return _Head.apply(_flat(y_pred), _flat(y_pred_fake), kind, 2)
+
+
+# ---------------------------------------------------------------- LeCam regularisation (--rgan_lecam)
+def _lecam_run(r, f, reg, need_r, need_f, dr=None, df=None):
+    """One D step's LeCam term on this rank's outputs: (float64[4] whose first element is the term,
+    dr, df), with ``reg``'s anchors moved.  One rank: one fused launch.  Data parallel: the
+    gradients and four partial sums, one all-reduce of those four doubles, the finish launch."""
+    if not dp.active():
+        return K.lecam(r, f, reg.hyper, reg.state, need_dr=need_r, need_df=need_f, dr=dr, df=df)
+    n_global = (r if r is not None else f).numel() * dp.world()
+    sums, dr, df = K.lecam(r, f, reg.hyper, reg.state, n_global, partial=True, need_dr=need_r, need_df=need_f,
+                           dr=dr, df=df)
+    dp.all_reduce_sum(sums)
+    K.lecam_finish(sums, n_global, (1 if r is not None else 0) | (2 if f is not None else 0), reg.hyper, reg.state)
+    return sums, dr, df
+
+
+def _times64(t, g):
+    """``_times`` under the float64 seed of the (float64) LeCam term."""
+    return _times(t, g if g is None or _is_unit(g) else g.to(torch.float32))
+
+
+class _LeCam(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, r, f, reg):
+        need_r = r is not None and ctx.needs_input_grad[0]
+        need_f = f is not None and ctx.needs_input_grad[1]
+        out, dr, df = _lecam_run(r, f, reg, need_r, need_f)
+        ctx.save_for_backward(dr, df)
+        return out[0]
+
+    @staticmethod
+    def backward(ctx, g):
+        dr, df = ctx.saved_tensors
+        return _times64(dr, g), _times64(df, g), None
+
+
+def lecam(y_real, y_fake, reg):
+    """The LeCam term of a D step (float64 scalar) on D's outputs on the real and
+    on the generated batch, either of which may be None (the separate backwards of heads 1-4), and
+    the move of ``reg``'s anchors (lecam.LeCam).  One launch computes the term and both input
+    gradients; the anchors are constants of the step."""
+    if y_real is None and y_fake is None:
+        raise ValueError("lecam: y_real or y_fake (or both) must be given")
+    return _LeCam.apply(_flat(y_real), _flat(y_fake), reg)
+
+
+class _LeCamCat(torch.autograd.Function):
+    """``lecam`` on the batched pass's joint output y = [D(x); D(x_fake)]: one autograd input, the
+    gradient written into one [2B] buffer (no concatenation), as ``_HeadCat``."""
+
+    @staticmethod
+    def forward(ctx, y, reg):
+        B = y.numel() // 2
+        yf = y.reshape(-1)
+        dy = torch.empty_like(yf)
+        out, _, _ = _lecam_run(yf[:B], yf[B:], reg, True, True, dr=dy[:B], df=dy[B:])
+        ctx.save_for_backward(dy)
+        ctx.shape = y.shape
+        return out[0]
+
+    @staticmethod
+    def backward(ctx, g):
+        dy, = ctx.saved_tensors
+        return _times64(dy, g).view(ctx.shape), None
+
+
+def lecam_cat(y, reg):
+    """``lecam`` from the joint [D(x); D(x_fake)] output of the batched D pass."""
+    if y.numel() % 2:
+        raise ValueError(f"lecam_cat: y has {y.numel()} elements, expected an even count [real; fake]")
+    return _LeCamCat.apply(y, reg)
 
 
 # ---------------------------------------------------------------- gradient penalty

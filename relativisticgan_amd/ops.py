@@ -28,6 +28,8 @@ dispatcher-level tracers see the MI355X kernels as graph nodes (not opaque Pytho
   rgan::diffaug_p        the same, each group of a sample applied with probability p (--rgan_aug_p, --rgan_ada_target)
   rgan::diffaug_p_backward
   rgan::ada_update_      rank statistic of a D step and the controller of p (--rgan_ada_target, mutating)
+  rgan::lecam_           LeCam term of a D step, its gradients and the move of its anchors (--rgan_lecam, mutating; not in the reference)
+  rgan::lecam_finish_    the same from the ranks' summed partial sums (data parallel, mutating)
   rgan::adam_            torch.optim.Adam's single-tensor step (mutating)          GLI:659,712
   rgan::ema_update_      moving average of G's weights (--rgan_ema_G, mutating; not in the reference)
 
@@ -631,6 +633,38 @@ def _(y_real, y_fake, hyper, state, adjust):
     return None
 
 
+# ------------------------------------------------------------------ LeCam regularisation of D
+@torch.library.custom_op("rgan::lecam_", mutates_args=("state", "dy_real", "dy_fake", "out"), device_types=_DEV)
+def lecam_(y_real: Optional[torch.Tensor], y_fake: Optional[torch.Tensor], hyper: torch.Tensor, state: torch.Tensor,
+           dy_real: Optional[torch.Tensor], dy_fake: Optional[torch.Tensor], out: torch.Tensor, n_global: int,
+           partial: bool) -> None:
+    """The LeCam term of one D step on D's outputs (either side may be None): the gradients into
+    ``dy_real`` / ``dy_fake`` (None: not formed), and into ``out`` = double[4] the term with
+    state = double[4] {a_real, a_fake, calls, 0} moved, or with ``partial`` this rank's four sums
+    with state left alone (hyper = double[4] {lambda, beta, start, 0}; include/rgan.h rgan_lecam)."""
+    K.lecam(y_real, y_fake, hyper, state, n_global, partial, need_dr=dy_real is not None,
+            need_df=dy_fake is not None, dr=dy_real, df=dy_fake, out=out)
+
+
+@lecam_.register_fake
+def _(y_real, y_fake, hyper, state, dy_real, dy_fake, out, n_global, partial):
+    return None
+
+
+@torch.library.custom_op("rgan::lecam_finish_", mutates_args=("state", "loss"), device_types=_DEV)
+def lecam_finish_(sums: torch.Tensor, n_global: int, sides: int, hyper: torch.Tensor, state: torch.Tensor,
+                  loss: torch.Tensor) -> None:
+    """The ranks' summed partial sums of ``rgan::lecam_`` turned into the term (``loss`` =
+    double[4], first element) and the move of the anchors in ``state`` (sides: 1 real, 2 fake,
+    3 both; include/rgan.h rgan_lecam_finish)."""
+    K.lecam_finish(sums, n_global, sides, hyper, state, loss)
+
+
+@lecam_finish_.register_fake
+def _(sums, n_global, sides, hyper, state, loss):
+    return None
+
+
 # ------------------------------------------------------------------ traced layers (nets)
 def tracing(t):
     """A trace (torch.export / torch.compile / fake-tensor propagation) rather than a run."""
@@ -663,4 +697,5 @@ def layer_forward(layer, h, training):
 OPS = ("conv2d", "conv2d_dgrad", "conv2d_wgrad", "channel_sum", "act_backward", "batch_norm_stats_",
        "batch_norm_apply", "batch_norm_backward", "spectral_power_", "spectral_scale", "spectral_backward", "loss_head",
        "loss_head_grad", "gp_penalty", "gp_penalty_backward", "gp_zc_penalty", "gp_zc_penalty_backward", "diffaug",
-       "diffaug_backward", "diffaug_p", "diffaug_p_backward", "adam_", "ema_update_", "ada_update_")
+       "diffaug_backward", "diffaug_p", "diffaug_p_backward", "adam_", "ema_update_", "ada_update_", "lecam_",
+       "lecam_finish_")

@@ -17,7 +17,9 @@ the real / generated batch D saw (after errD and the WGAN-GP penalty), in the it
 transforms of ``--rgan_diffaug`` are gated per sample with a probability p (one more draw, the
 gates, after each draw of the transforms' uniforms); under adaptation every D step's outputs move
 p (augment.AdaptiveP), the log line ends with ``ada_p: ... r: ...`` and checkpoints gain the
-key ``ada``.
+key ``ada``.  With ``--rgan_lecam`` the LeCam term (losses.lecam) joins the backward
+that carries errD -- no further pass of D --, every D step moves its anchors (lecam.LeCam), the
+log line ends with ``lecam: ... a_real: ... a_fake: ...`` and checkpoints gain the key ``lecam``.
 """
 import os
 import random
@@ -28,11 +30,12 @@ import numpy
 import torch
 
 from . import augment, autograd, dp
-from .config import TITLES, parse, reg_weight, validate_ada, validate_reg
+from .config import LECAM_DEFAULTS, TITLES, parse, reg_weight, validate_ada, validate_lecam, validate_reg
 from .ema import GeneratorEMA
 from .kernels import DeviceRNG
-from .losses import (gradient_penalty, loss_D, loss_D_cat, loss_D_fake, loss_D_real, loss_G, loss_G_cat, unit_seed,
-                     zero_centered_penalty)
+from .lecam import LeCam
+from .losses import (gradient_penalty, lecam, lecam_cat, loss_D, loss_D_cat, loss_D_fake, loss_D_real, loss_G,
+                     loss_G_cat, unit_seed, zero_centered_penalty)
 from .nets import DCGAN_D, DCGAN_G, weights_init
 from .optim import Adam
 from .perf import ThroughputMeter
@@ -125,6 +128,11 @@ class Trainer:
         self.r2 = float(getattr(p, "rgan_r2", 0.0) or 0.0)
         self.reg_every = int(getattr(p, "rgan_reg_every", 1) or 1)
         validate_reg(self.r1, self.r2, self.reg_every, self.pac)
+        # --rgan_lecam: the term's anchors and hyper-parameters on the device (None = off: no
+        # object, no call, no checkpoint key)
+        lc = (getattr(p, "rgan_lecam", 0.0) or 0.0, getattr(p, "rgan_lecam_beta", LECAM_DEFAULTS[0]),
+              getattr(p, "rgan_lecam_start", LECAM_DEFAULTS[1]))
+        self.lecam = LeCam(self.device, *lc) if validate_lecam(*lc) else None
         # one batched D pass per D step where the nets allow it (--rgan_batch_D).  Default
         # (auto): on, under data parallelism too.  G's gradient buckets all-reduce while G's
         # own backward runs (GradReducer), so the deferred G step (flush, right before the
@@ -139,7 +147,7 @@ class Trainer:
         bg = getattr(p, "rgan_batch_G", None)
         self.batch_G = (True if bg is None else bool(bg)) and self.pac == 1 and self.D.segmentable
         self._fake_D = None
-        self._one = None
+        self._one = self._one64 = None
         self.errD = self.errG = None
         self.last = {}
         # set by whoever captures iterations into HIP graphs (bench.py, dp.PiecewiseGraph users):
@@ -248,14 +256,21 @@ class Trainer:
         if red is not None:
             red.arm()
 
-    def _backward(self, loss):
+    def _backward(self, loss, term=None):
         """loss.backward() (GLI:605/624/644/658/710) with a cached device 1.0 as the seed
-        gradient (autograd would fill a fresh ones tensor on every call)."""
+        gradient (autograd would fill a fresh ones tensor on every call).  ``term``: the
+        (float64) LeCam term of the same outputs of D, a second root of the same backward."""
         one = self._one
         if one is None or one.device != loss.device or one.dtype != loss.dtype:
             one = self._one = unit_seed(loss.device, loss.dtype)
         with autograd.owning_grads():  # the fused layers write their weight .grad directly
-            loss.backward(one)
+            if term is None:
+                loss.backward(one)
+                return
+            one64 = self._one64
+            if one64 is None or one64.device != term.device:
+                one64 = self._one64 = unit_seed(term.device, term.dtype)
+            torch.autograd.backward((loss, term), (one, one64))
 
     def _set_D_grad(self, flag):
         for q in self.D.parameters():
@@ -311,14 +326,17 @@ class Trainer:
                 # heads 1-4: err_real.backward(); err_fake.backward() accumulate = one backward
                 # of the sum (GLI:605, 624); heads 5-8: errD.backward() (GLI:644)
                 errD = loss_D_cat(kind, y_all)
+                lc = lecam_cat(y_all, self.lecam) if self.lecam is not None else None
                 if last_bwd == "errD":
                     self._arm(self.redD)
-                self._backward(errD)
+                self._backward(errD, lc)
                 errD = errD.detach()
             elif kind <= 4:
                 y_pred = D(x)
                 err_real = loss_D_real(kind, y_pred)
-                self._backward(err_real)
+                # (--rgan_lecam: the real side joins this backward, the fake side err_fake's)
+                lc_real = lecam(y_pred, None, self.lecam) if self.lecam is not None else None
+                self._backward(err_real, lc_real)
                 if z is None:
                     z = self._normal(feed, "z_D", zshape)
                 self.flush()
@@ -327,10 +345,13 @@ class Trainer:
                     x_fake = self._augment(x_fake, u_aug, gate, slice(self.B, None))
                 y_pred_fake = D(x_fake)
                 err_fake = loss_D_fake(kind, y_pred_fake)
+                lc = lecam(None, y_pred_fake, self.lecam) if self.lecam is not None else None
                 if last_bwd == "errD":
                     self._arm(self.redD)
-                self._backward(err_fake)
+                self._backward(err_fake, lc)
                 errD = err_real.detach() + err_fake.detach()
+                if lc is not None:
+                    lc = lc_real.detach() + lc.detach()
             else:
                 y_pred = D(x)
                 if z is None:
@@ -341,13 +362,16 @@ class Trainer:
                     x_fake = self._augment(x_fake, u_aug, gate, slice(self.B, None))
                 y_pred_fake = D(x_fake)
                 errD = loss_D(kind, y_pred, y_pred_fake)
+                lc = lecam(y_pred, y_pred_fake, self.lecam) if self.lecam is not None else None
                 if last_bwd == "errD":
                     self._arm(self.redD)
-                self._backward(errD)
+                self._backward(errD, lc)
             rec = {"x": x_raw, "z": z, "y_pred": y_pred.detach(), "y_pred_fake": y_pred_fake.detach(),
                    "errD": errD.detach()}
             if self.aug:
                 rec.update(aug=u_aug, x_aug=x, x_fake_aug=x_fake)
+            if self.lecam is not None:
+                rec.update(lecam=lc.detach())
             if self.ada is not None:
                 rec.update(gate=gate)
                 self.ada.update(rec["y_pred"], rec["y_pred_fake"])  # (nothing without --rgan_ada_target)
@@ -488,6 +512,8 @@ class Trainer:
             st["G_ema"] = self.ema.state_dict()
         if self.ada is not None:  # (collective under DP: the pair counts of every rank)
             st["ada"] = self.ada.state_dict()
+        if self.lecam is not None:  # (no collective: the ranks hold the same anchors)
+            st["lecam"] = self.lecam.state_dict()
         return st
 
     def load(self, ckpt):
@@ -508,6 +534,11 @@ class Trainer:
                 self.ada.load_state_dict(ckpt["ada"])
             else:  # written by the reference or with the flags off: start as the flags say
                 self.ada.restart()
+        if self.lecam is not None:
+            if "lecam" in ckpt:
+                self.lecam.load_state_dict(ckpt["lecam"])
+            else:  # written by the reference or with the flag off: the anchors start afresh
+                self.lecam.restart()
         self.z_test.copy_(self._shard(ckpt["z_test"].to(self.device)) if ckpt["z_test"].shape[0] != self.B
                           else ckpt["z_test"])
         return ckpt["i"], ckpt["current_set_images"]
@@ -518,6 +549,8 @@ class Trainer:
         line = '[%d] Diff: %.4f loss_D: %.4f loss_G: %.4f time:%.4f' % (i, -d + g, d, g, elapsed)
         if self.ada is not None:
             line += ' ada_p: %.4f r: %.4f' % self.ada.read()
+        if self.lecam is not None:
+            line += ' lecam: %.4f a_real: %.4f a_fake: %.4f' % ((self.last["D"]["lecam"].item(),) + self.lecam.read())
         return line
 
 
