@@ -6,9 +6,11 @@
 // Numerics: per-thread sums are accumulated in double (torch's CPU kernel uses a double
 // accumulator too): the backward sums sum(g) and sum(g*(y-mean)) can cancel almost
 // completely when the upstream gradient lies near BN's null space, and a float sum
-// there leaves a coherent per-channel offset in dy.  Forward moments use shifted sums
-// (shift = the thread's first sample) in double; partials are merged with Chan's
-// parallel formula in a fixed order (deterministic, no E[x^2]-E[x]^2 cancellation).
+// there leaves a coherent per-channel offset in dy.  Forward moments use shifted sums in
+// double with ONE shift per channel (its first pixel, y[0][c]), the difference y - shift
+// itself formed in double; the chunk partials are plain sums, added in a fixed order
+// (deterministic; the shift keeps E[x^2]-E[x]^2 from cancelling).  Chan's parallel
+// formula merges the moments of ranks only (bn_finalize_kernel).
 //
 // Layout/perf: the vector path gives every thread a fixed quad of 4 channels (float4
 // loads, no per-element index division) and walks pixels; HBM-bound with algorithmic
@@ -99,7 +101,9 @@ __device__ __forceinline__ void chan_merge(double& N, double& M, double& S, doub
 // ------------------------------------------------------------------ forward moments
 // Shifted sums with ONE shift per channel (its first pixel, y[0][c]) shared by every
 // block: partials are plain (sum d, sum d^2), d = y - shift, accumulated in double, so
-// the merge is a division-free parallel sum.  partial layout: [chunk][2][C] doubles.
+// the merge is a division-free parallel sum.  d itself is formed in double: an fp32 y - shift
+// rounds (2^-24 |d| per sample), and in a channel whose mean is small against its spread those
+// roundings reached 1e-4 of the mean.  partial layout: [chunk][2][C] doubles.
 template <int Q>
 __global__ __launch_bounds__(256) void bn_moments_partial(const float* __restrict__ y, long long P, int C,
                                                           long long sp, long long sc, int tpr, long long rows,
@@ -117,7 +121,7 @@ __global__ __launch_bounds__(256) void bn_moments_partial(const float* __restric
     auto acc = [&](const float (&v)[Q]) {
 #pragma unroll
       for (int q = 0; q < Q; ++q) {
-        const double d = (double)(v[q] - sft[q]);
+        const double d = (double)v[q] - (double)sft[q];
         s1[q] += d;
         s2[q] += d * d;
       }

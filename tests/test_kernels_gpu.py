@@ -1113,7 +1113,8 @@ def test_device_rng(K):
 
 def test_bn_two_segments_one_launch(K):
     """rgan_bn_segment_stats_n + rgan_bn_apply_segments (the batched D pass's two calls in
-    one launch each) == the two calls one at a time, bitwise, incl. the running statistics."""
+    one launch each) == the two calls one at a time, bitwise, incl. the running statistics.
+    (Kernel against kernel; each of them against float64: tests/test_bn_first_order_gpu.py.)"""
     from relativisticgan_amd.kernels import ConvGeom
     torch.manual_seed(17)
     g = ConvGeom(4, 2, 1, False)
@@ -1152,7 +1153,8 @@ def test_bn_segment_apply_one_call(K, B, cin, H, cout, tr, nseg):
     == rgan_bn_segment_stats_n + rgan_bn_apply_segments: stats / output / running statistics
     within 1e-6 (the one-launch merge adds the segments' double sums in another order: equal
     after rounding to fp32 but for rare ties) and bitwise on the two-launch path;
-    num_batches_tracked counted once per batch segment."""
+    num_batches_tracked counted once per batch segment.  (Each side of the launch rule against
+    float64 from synthesised segment sums: tests/test_bn_first_order_gpu.py test_segment_apply.)"""
     from relativisticgan_amd.kernels import ConvGeom
     torch.manual_seed(29)
     g = ConvGeom(4, 2, 1, tr)
@@ -1274,7 +1276,9 @@ def test_bn_backward_two_segments(K, C, B, H):
     backward sums + apply: dy and the summed affine gradients -- bitwise for the three-launch
     path (4096 rows per call), within 1e-6 for the one-launch small-layer kernel
     (bn_bwd_small: <= 2048 rows per call, e.g. the 4x4 layer under D's dense layer), whose
-    double sums associate differently; and rgan_bn_backward (one call) likewise."""
+    double sums associate differently; and rgan_bn_backward (one call) likewise.  (The stats here
+    are random, not the batch's; with true statistics against float64:
+    tests/test_bn_first_order_gpu.py test_backward_segments.)"""
     torch.manual_seed(19)
     small = (B // 2) * H * H <= 2048
     same = (lambda a, b: torch.allclose(a, b, rtol=1e-6, atol=1e-6)) if small else torch.equal
@@ -1320,7 +1324,8 @@ def test_dgrad_post_op(K, case, mode):
     """rgan_conv_post (the layer below's first backward pass in the data-gradient GEMM's
     epilogue / split-K reduce) == conv_dgrad followed by that pass: mode 1 = act_backward
     (LeakyReLU, Tanh), mode 2 = bn_backward (g = da * act', the BatchNorm sums, then
-    bn_backward_parts) with 1 and 2 batch segments."""
+    bn_backward_parts) with 1 and 2 batch segments.  (Mode 2 against the float64 conv gradient
+    and BatchNorm backward: tests/test_bn_first_order_gpu.py test_backward_parts.)"""
     from relativisticgan_amd.kernels import ConvGeom, Post
     B, cin, cout, H, tr = case
     torch.manual_seed(23)
