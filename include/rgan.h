@@ -29,8 +29,8 @@ extern "C" {
  * call's uint32 arrival ticket, zero before the first call); revision 1 took float[1].
  * 3: adds rgan_conv_wgrad_rows.  4: adds rgan_bn_segment_apply and rgan_bn_backward_sums_apply.
  * rgan_diffaug_workspace, rgan_diffaug, rgan_ema_update, rgan_diffaug_p, rgan_ada_update,
- * rgan_ada_adjust, rgan_lecam and rgan_lecam_finish are additive within revision 4 (nothing else
- * changed). */
+ * rgan_ada_adjust, rgan_lecam, rgan_lecam_finish, rgan_diffaug_geo_workspace and rgan_diffaug_geo
+ * are additive within revision 4 (nothing else changed). */
 #define RGAN_ABI_VERSION 4
 
 /* Activation codes fused into epilogues (GLI:345,370,388,417,437,450; SELU GLI:338). */
@@ -527,6 +527,35 @@ int rgan_diffaug(const float* x, const float* u, int batch, int channels, int h,
 int rgan_diffaug_p(const float* x, const float* u, const float* gate, const double* p, int batch,
                    int channels, int h, int w, int policy, int adjoint, float* ws, float* y,
                    void* stream);
+
+/* ---- geometric groups of the same transform: x-flip, quarter turns, warp (--rgan_diffaug) ----
+ * (additive within ABI revision 4: no existing entry point changed)
+ * policy in [0, 63]: bits 1, 2, 4 as rgan_diffaug, bit 8 xflip, bit 16 rot90 (needs h == w),
+ * bit 32 warp.  v: [batch][8] uniforms in [0, 1): v0 flip, v1 quarter turns, v2 zoom, v3 angle,
+ * v4..v6 the gates of xflip / rot90 / warp (read only with gate and p, which also gate colour /
+ * translation / cutout as rgan_diffaug_p does), v7 reserved.  A cleared or closed group takes
+ * its identity value.
+ *   flip  = v0 >= 1/2                       torch.flip(., (3,))
+ *   k     = min(floor(4 v1), 3)             torch.rot90(., k, (2, 3))
+ *   s     = 2^((v2 - 1/2) / 2), theta = (2 v3 - 1) pi   (derived in double)
+ *   y = cutout( translate( Warp( Rot90^k( Flip( col(x) ) ) ) ) ), the colour means those of x and
+ *   the box tested at the output position.  With ci = (h-1)/2, cj = (w-1)/2, di = i + tx - ci,
+ *   dj = j + ty - cj:
+ *     r = ci + ( cos(theta) di + sin(theta) dj) / s,  c = cj + (-sin(theta) di + cos(theta) dj) / s
+ *     Warp(z)[i,j] = sum over the four lattice neighbours q of (r, c) inside the image of
+ *                    max(0, 1 - |r - q_r|) max(0, 1 - |c - q_c|) z[q]
+ * Coordinates are computed in double.  A sample whose warp is closed, cleared or the identity
+ * (v2 = v3 = 1/2) is moved by whole pixels: without the colour bit its outputs are copied inputs
+ * or +0.0, with it the arithmetic is rgan_diffaug's.  adjoint != 0: the exact transpose of the
+ * linear part, gathered over the at most 4 x 4 outputs that read a source pixel, in a fixed
+ * order: no atomics, two calls give the same bits.  gate and p: both null (ungated) or both
+ * non-null; exactly one null is RGAN_EINVAL, as are bit 16 with h != w and a policy outside
+ * [0, 63].  With bits 8, 16, 32 clear the call is rgan_diffaug / rgan_diffaug_p (v unread).
+ * Sizes, aliasing and workspace as rgan_diffaug (rgan_diffaug_geo_workspace floats). */
+size_t rgan_diffaug_geo_workspace(int batch, int channels, int h, int w);
+int rgan_diffaug_geo(const float* x, const float* u, const float* v, const float* gate, const double* p,
+                     int batch, int channels, int h, int w, int policy, int adjoint, float* ws, float* y,
+                     void* stream);
 
 /* ---- adaptive augmentation probability (--rgan_ada_target; no reference counterpart) ----
  * (additive within ABI revision 4: no existing entry point changed)

@@ -136,6 +136,9 @@ _SIGS = {
     "rgan_diffaug_workspace": (c_sz, [c_int, c_int, c_int, c_int]),
     "rgan_diffaug": (c_int, [c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_int, c_vp, c_vp, c_vp]),
     "rgan_diffaug_p": (c_int, [c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_int, c_vp, c_vp, c_vp]),
+    "rgan_diffaug_geo_workspace": (c_sz, [c_int, c_int, c_int, c_int]),
+    "rgan_diffaug_geo": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_int, c_vp, c_vp,
+                                 c_vp]),
     "rgan_ema_update": (c_int, [c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "rgan_ada_update": (c_int, [c_vp, c_vp, c_int, c_vp, c_vp, c_int, c_vp]),
     "rgan_ada_adjust": (c_int, [c_vp, c_vp, c_vp]),

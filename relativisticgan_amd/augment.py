@@ -1,10 +1,11 @@
 """Differentiable augmentation of D's inputs (``--rgan_diffaug``; the reference has none).
 
 The same family of random transforms -- colour (brightness, saturation, contrast), translation,
-cutout -- is applied to every image D sees, reals and fakes alike, each sample with its own
-parameters, and the generator's gradient flows back through it (DESIGN §3 has the algebra,
-include/rgan.h rgan_diffaug the kernel).  This module holds the policy parsing, the draw of
-the per-sample uniforms and the autograd node the training step uses.
+cutout, and the geometric x-flip, quarter turns and warp (zoom with rotation) -- is applied to
+every image D sees, reals and fakes alike, each sample with its own parameters, and the
+generator's gradient flows back through it (DESIGN §3 has the algebra, include/rgan.h
+rgan_diffaug / rgan_diffaug_geo the kernels).  This module holds the policy parsing, the draw
+of the per-sample uniforms and the autograd node the training step uses.
 
 ``--rgan_aug_p`` / ``--rgan_ada_target`` set the augmentation's strength: each of a sample's
 three transform groups is applied with probability p (one more row of uniforms per sample, the
@@ -17,13 +18,16 @@ from . import dp
 from . import kernels as K
 from . import ops  # noqa: F401  (registers rgan::ada_update_)
 
-BITS = {"color": 1, "translation": 2, "cutout": 4}
+BITS = {"color": 1, "translation": 2, "cutout": 4, "xflip": 8, "rot90": 16, "warp": 32}
+GEO = 8 | 16 | 32  # the groups of rgan_diffaug_geo: they take a row of uniforms of their own
 COLUMNS = 8  # uniforms per sample: 0..6 used, 7 reserved
+GEO_COLUMNS = 8  # flip, quarter turns, zoom, angle, the three gates, reserved
 GATE_COLUMNS = 4  # gates per sample: colour, translation, cutout, reserved
 
 
 def parse_policy(policy):
-    """``"color,translation,cutout"`` or any subset -> the kernel's bitmask ('' / None: 0, off)."""
+    """``"color,translation,cutout,xflip,rot90,warp"`` or any subset -> the kernel's bitmask
+    ('' / None: 0, off)."""
     mask = 0
     for name in (policy or "").split(","):
         name = name.strip()
@@ -52,6 +56,15 @@ def draw(rows, host, dev_rng=None):
     return dev_rng.uniform((rows, COLUMNS))
 
 
+def draw_geo(rows, host, dev_rng=None):
+    """[rows][8] uniforms in [0, 1) of the geometric groups for the GLOBAL batch, from the
+    generator ``draw`` uses (the caller draws them last, after the gates, and only when the
+    policy has a geometric bit, so the other policies keep their random-number stream)."""
+    if host:
+        return torch.rand(rows, GEO_COLUMNS)
+    return dev_rng.uniform((rows, GEO_COLUMNS))
+
+
 def draw_gates(rows, host, dev_rng=None):
     """[rows][4] gate uniforms in [0, 1) for the GLOBAL batch, from the generator ``draw`` uses
     (the caller draws them directly after it and shards them the same way)."""
@@ -65,25 +78,30 @@ class _DiffAug(torch.autograd.Function):
     under the forward's gates and p when it was gated."""
 
     @staticmethod
-    def forward(ctx, x, u, policy, out, gate, p):
+    def forward(ctx, x, u, policy, out, gate, p, geo):
         ctx.policy = policy
-        ctx.gated = gate is not None
-        ctx.save_for_backward(*((u, gate, p) if ctx.gated else (u,)))
-        return K.diffaug(x, u, policy, out=out, gate=gate, p=p)
+        ctx.gated, ctx.geo = gate is not None, geo is not None
+        ctx.save_for_backward(*(t for t in (u, gate, p, geo) if t is not None))
+        return K.diffaug(x, u, policy, out=out, gate=gate, p=p, geo=geo)
 
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, g):
-        u, gate, p = ctx.saved_tensors if ctx.gated else (*ctx.saved_tensors, None, None)
-        return K.diffaug(g, u, ctx.policy, adjoint=True, gate=gate, p=p), None, None, None, None, None
+        saved = list(ctx.saved_tensors)
+        u = saved.pop(0)
+        gate, p = (saved.pop(0), saved.pop(0)) if ctx.gated else (None, None)
+        geo = saved.pop(0) if ctx.geo else None
+        return (K.diffaug(g, u, ctx.policy, adjoint=True, gate=gate, p=p, geo=geo), None, None, None, None, None,
+                None)
 
 
-def apply(x, u, policy, out=None, gate=None, p=None):
+def apply(x, u, policy, out=None, gate=None, p=None, geo=None):
     """T(x); carries autograd back to ``x`` when it requires grad (the G step's T(G(z))).
-    ``gate`` ([B][4] uniforms) and ``p`` (a device double) apply each group with probability p."""
+    ``gate`` ([B][4] uniforms) and ``p`` (a device double) apply each group with probability p;
+    ``geo`` ([B][8] uniforms) goes with a policy that has a geometric bit."""
     if x.requires_grad and torch.is_grad_enabled():
-        return _DiffAug.apply(x, u, policy, out, gate, p)
-    return K.diffaug(x, u, policy, out=out, gate=gate, p=p)
+        return _DiffAug.apply(x, u, policy, out, gate, p, geo)
+    return K.diffaug(x, u, policy, out=out, gate=gate, p=p, geo=geo)
 
 
 class AdaptiveP:

@@ -22,7 +22,7 @@ FLAGS = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-I" + os.path.
 # about half, then <= 6 s each; the pool below starts them in this order)
 SOURCES = ["gemm_wgrad.hip", "gemm_conv.hip", "gemm_convt2.hip", "conv_gemm.hip", "bn_act.hip", "first_layer.hip",
            "heads_optim.hip", "images.hip", "augment.hip", "ema.hip", "sampling.hip", "patches.hip", "upsample.hip",
-           "gp_zc.hip", "ada.hip", "lecam.hip"]
+           "gp_zc.hip", "ada.hip", "lecam.hip", "augment_geo.hip"]
 
 
 def _stale(obj, src):

@@ -87,8 +87,10 @@ def make_parser(script="GAN_losses_iter"):
                         "channel-wise)")
     p.add_argument("--rgan_diffaug", default="",
                    help="differentiable augmentation of every image D sees, reals and fakes, with G's gradient "
-                        "flowing back through it: a comma-separated subset of color,translation,cutout "
-                        "(default '': off; not with --rgan_pac 2)")
+                        "flowing back through it: a comma-separated subset of color,translation,cutout,"
+                        "xflip,rot90,warp (default '': off; not with --rgan_pac 2; the geometric xflip, rot90 "
+                        "and warp leak into G when always on: give them --rgan_aug_p <= 0.8 or "
+                        "--rgan_ada_target)")
     p.add_argument("--rgan_aug_p", type=float, default=None,
                    help="apply each --rgan_diffaug transform to a sample with this probability, in [0, 1]: the "
                         "fixed value, or with --rgan_ada_target the initial one (default unset: 1 without "

@@ -20,59 +20,11 @@
 // over 64 blocks.  VEC = 4 (16-byte loads and stores) needs W % 4 == 0 and 16-byte aligned
 // tensors; a sample whose column shift is not a multiple of 4 then loads its sources as
 // scalars and still stores 16 bytes.  Other widths run the VEC = 1 instantiation.
-#include "common.h"
+#include "augment.h"
 
 #include <climits>
 
 namespace rgan {
-
-struct AugParam {
-  float beta, sat, con;
-  int tx, ty;          // source of output (i, j) is (i + tx, j + ty)
-  int r0, r1, c0, c1;  // cutout box, inclusive (empty: r1 < r0)
-};
-
-// min(floor(u n), n - 1), clamped below too (u is caller data: every index derived from it
-// stays in range whatever it holds).  The product is exact in double.
-__device__ __forceinline__ int aug_pick(float u, int n) {
-  const int v = (int)floor((double)u * (double)n);
-  return v < 0 ? 0 : (v > n - 1 ? n - 1 : v);
-}
-
-__device__ __forceinline__ AugParam aug_param(const float* __restrict__ u, int b, int H, int W, int policy) {
-  const float* r = u + 8LL * b;
-  AugParam p;
-  const bool colour = policy & 1;
-  p.beta = colour ? r[0] - 0.5f : 0.f;
-  p.sat = colour ? 2.f * r[1] : 1.f;
-  p.con = colour ? r[2] + 0.5f : 1.f;
-  p.tx = p.ty = 0;
-  if (policy & 2) {
-    const int Rh = (H + 4) / 8, Rw = (W + 4) / 8;  // floor(H / 8 + 1/2)
-    p.tx = aug_pick(r[3], 2 * Rh + 1) - Rh;
-    p.ty = aug_pick(r[4], 2 * Rw + 1) - Rw;
-  }
-  p.r0 = p.c0 = 0;
-  p.r1 = p.c1 = -1;
-  if (policy & 4) {
-    const int Kh = (H + 1) / 2, Kw = (W + 1) / 2;  // floor(H / 2 + 1/2)
-    p.r0 = aug_pick(r[5], H + 1 - (Kh & 1)) - Kh / 2;
-    p.r1 = p.r0 + Kh - 1;
-    p.c0 = aug_pick(r[6], W + 1 - (Kw & 1)) - Kw / 2;
-    p.c1 = p.c0 + Kw - 1;
-  }
-  return p;
-}
-
-// rgan_diffaug_p: `policy` restricted to the groups sample b's gates open, gate[b][g] < (float)*p
-// (strict; columns 0, 1, 2 = colour, translation, cutout).  Everything downstream sees that
-// mask as the sample's policy, so a closed group takes the same path as a cleared policy bit.
-__device__ __forceinline__ int aug_open(const float* __restrict__ gate, const double* __restrict__ prob, int b,
-                                        int policy) {
-  const float p = (float)prob[0];
-  const float* g = gate + 4LL * b;
-  return policy & ((g[0] < p ? 1 : 0) | (g[1] < p ? 2 : 0) | (g[2] < p ? 4 : 0));
-}
 
 // ws[b][blockIdx.x] = this block's share of the sample sum: of x (forward), or of the dy
 // positions the adjoint scatters back (not cut out, target inside the image).  Block k sums
@@ -234,11 +186,6 @@ __global__ __launch_bounds__(256) void aug_apply(const float* __restrict__ in, c
     for (int k = 0; k < VEC; ++k) o[k] = colour_map(v[k], m[k] * inv_c, ok[k]);
     store(c, o);
   }
-}
-
-// reduction blocks per sample for `items` work items: ~1024 items (four per thread) each
-static inline int aug_blocks(long long items) {
-  return (int)std::min<long long>(std::max<long long>((items + 1023) / 1024, 1), 64);
 }
 
 }  // namespace rgan

@@ -1155,18 +1155,35 @@ def gather_images(images, idx, out=None):
 
 
 # ------------------------------------------------------------------ differentiable augmentation
-def diffaug(x, u, policy, adjoint=False, out=None, gate=None, p=None):
+def diffaug(x, u, policy, adjoint=False, out=None, gate=None, p=None, geo=None):
     """The per-sample colour / translation / cutout transform of include/rgan.h rgan_diffaug
     (``policy``: bit 1 colour, 2 translation, 4 cutout; ``u``: [B][8] uniforms), or with
     ``adjoint`` its transpose applied to a gradient.  ``out``: a contiguous buffer other than
     ``x`` (e.g. half of a batched D input).  With ``gate`` ([B][4] uniforms) and ``p`` (a device
-    double) each group of a sample is applied iff its gate is below p (rgan_diffaug_p)."""
+    double) each group of a sample is applied iff its gate is below p (rgan_diffaug_p).
+    ``policy`` >= 8 (bit 8 x-flip, 16 quarter turns, 32 warp) needs ``geo``, the [B][8] uniforms
+    of those groups, and runs rgan_diffaug_geo; below 8 ``geo`` is not read."""
     L.require_cuda(x, u, out)
+    policy = int(policy)
+    if policy >= 8:
+        if policy > 63:
+            raise L.RganError(f"diffaug: policy must lie in [0, 63], got {policy}")
+        if geo is None:
+            raise L.RganError("diffaug: policy >= 8 (xflip / rot90 / warp) needs geo, their [B][8] uniforms")
+        if not (torch.is_tensor(geo) and geo.is_cuda and geo.device == x.device):
+            raise L.RganError("diffaug: geo must be a tensor on x's device")
+        if geo.dtype != torch.float32 or geo.dim() != 2 or geo.shape[1] != 8 or not geo.is_contiguous():
+            raise L.RganError(f"diffaug: geo must be a contiguous float32 [B][8] tensor, got {geo.dtype} "
+                              f"{tuple(geo.shape)}")
     if x.dim() != 4 or x.dtype != torch.float32 or u.dtype != torch.float32:
         raise L.RganError("diffaug: x must be a float32 [B][C][H][W] tensor and u float32")
     B, C, H, W = x.shape
     if tuple(u.shape) != (B, 8):
         raise L.RganError(f"diffaug: u must be [{B}][8] (one row of uniforms per sample), got {tuple(u.shape)}")
+    if policy >= 8 and geo.shape[0] != B:
+        raise L.RganError(f"diffaug: geo must be [{B}][8] (one row of uniforms per sample), got {tuple(geo.shape)}")
+    if policy & 16 and H != W:
+        raise L.RganError(f"diffaug: rot90 (policy bit 16) needs a square image, got {H} x {W}")
     if (gate is None) != (p is None):
         raise L.RganError("diffaug: gate and p come together (both or neither)")
     if gate is not None:
@@ -1184,6 +1201,12 @@ def diffaug(x, u, policy, adjoint=False, out=None, gate=None, p=None):
     elif not out.is_contiguous() or out.shape != x.shape or out.dtype != torch.float32:
         raise L.RganError("diffaug: out must be contiguous float32 and shaped like x")
     lib = L.lib()
+    if policy >= 8:
+        ws = torch.empty(max(int(lib.rgan_diffaug_geo_workspace(B, C, H, W)), 1), dtype=torch.float32,
+                         device=x.device)
+        L.check(lib.rgan_diffaug_geo(L.ptr(x), L.ptr(u), L.ptr(geo), L.ptr(gate), L.ptr(p), B, C, H, W, policy,
+                                     int(bool(adjoint)), L.ptr(ws), L.ptr(out), L.stream()), "rgan_diffaug_geo")
+        return out
     ws = torch.empty(max(int(lib.rgan_diffaug_workspace(B, C, H, W)), 1), dtype=torch.float32, device=x.device)
     if gate is not None:
         L.check(lib.rgan_diffaug_p(L.ptr(x), L.ptr(u), L.ptr(gate), L.ptr(p), B, C, H, W, int(policy),

@@ -27,7 +27,9 @@ dispatcher-level tracers see the MI355X kernels as graph nodes (not opaque Pytho
   rgan::diffaug_backward its adjoint
   rgan::diffaug_p        the same, each group of a sample applied with probability p (--rgan_aug_p, --rgan_ada_target)
   rgan::diffaug_p_backward
-  rgan::ada_update_      rank statistic of a D step and the controller of p (--rgan_ada_target, mutating)
+  rgan::diffaug_geo      the same with the geometric groups, x-flip / quarter turns / warp (optional gate and p)
+  rgan::diffaug_geo_backward
+  rgan::ada_update_     rank statistic of a D step and the controller of p (--rgan_ada_target, mutating)
   rgan::lecam_           LeCam term of a D step, its gradients and the move of its anchors (--rgan_lecam, mutating; not in the reference)
   rgan::lecam_finish_    the same from the ranks' summed partial sums (data parallel, mutating)
   rgan::adam_            torch.optim.Adam's single-tensor step (mutating)          GLI:659,712
@@ -589,6 +591,52 @@ diffaug_p_backward.register_autograd(_no_double("diffaug_p_backward"),
                                      setup_context=lambda ctx, inputs, output: None)
 
 
+@torch.library.custom_op("rgan::diffaug_geo", mutates_args=(), device_types=_DEV)
+def diffaug_geo(x: torch.Tensor, u: torch.Tensor, geo: torch.Tensor, policy: int,
+                gate: Optional[torch.Tensor] = None, p: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """rgan::diffaug / rgan::diffaug_p with the geometric groups (policy bits 8 x-flip, 16 quarter
+    turns, 32 warp; geo [B][8] their uniforms; gate and p both or neither; include/rgan.h
+    rgan_diffaug_geo)."""
+    return K.diffaug(x, u, policy, gate=gate, p=p, geo=geo)
+
+
+@diffaug_geo.register_fake
+def _(x, u, geo, policy, gate=None, p=None):
+    return torch.empty(x.shape, dtype=torch.float32, device=x.device)
+
+
+def _aug_geo_setup(ctx, inputs, output):
+    x, u, geo, policy, gate, p = inputs
+    ctx.policy = policy
+    ctx.gated = gate is not None
+    ctx.save_for_backward(*((u, geo, gate, p) if ctx.gated else (u, geo)))
+
+
+def _aug_geo_backward(ctx, g):
+    u, geo, gate, p = ctx.saved_tensors if ctx.gated else (*ctx.saved_tensors, None, None)
+    return torch.ops.rgan.diffaug_geo_backward(g, u, geo, ctx.policy, gate, p), None, None, None, None, None
+
+
+diffaug_geo.register_autograd(_aug_geo_backward, setup_context=_aug_geo_setup)
+
+
+@torch.library.custom_op("rgan::diffaug_geo_backward", mutates_args=(), device_types=_DEV)
+def diffaug_geo_backward(g: torch.Tensor, u: torch.Tensor, geo: torch.Tensor, policy: int,
+                         gate: Optional[torch.Tensor] = None, p: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The adjoint of rgan::diffaug_geo applied to g (rgan_diffaug_geo with adjoint = 1), under the
+    gates and the p of the forward when it was gated."""
+    return K.diffaug(g, u, policy, adjoint=True, gate=gate, p=p, geo=geo)
+
+
+@diffaug_geo_backward.register_fake
+def _(g, u, geo, policy, gate=None, p=None):
+    return torch.empty(g.shape, dtype=torch.float32, device=g.device)
+
+
+diffaug_geo_backward.register_autograd(_no_double("diffaug_geo_backward"),
+                                       setup_context=lambda ctx, inputs, output: None)
+
+
 # ------------------------------------------------------------------ optimizer
 @torch.library.custom_op("rgan::adam_", mutates_args=("params", "exp_avgs", "exp_avg_sqs", "step"),
                          device_types=_DEV)
@@ -698,4 +746,4 @@ OPS = ("conv2d", "conv2d_dgrad", "conv2d_wgrad", "channel_sum", "act_backward", 
        "batch_norm_apply", "batch_norm_backward", "spectral_power_", "spectral_scale", "spectral_backward", "loss_head",
        "loss_head_grad", "gp_penalty", "gp_penalty_backward", "gp_zc_penalty", "gp_zc_penalty_backward", "diffaug",
        "diffaug_backward", "diffaug_p", "diffaug_p_backward", "adam_", "ema_update_", "ada_update_", "lecam_",
-       "lecam_finish_")
+       "lecam_finish_", "diffaug_geo", "diffaug_geo_backward")

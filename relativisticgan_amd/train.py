@@ -17,7 +17,8 @@ the real / generated batch D saw (after errD and the WGAN-GP penalty), in the it
 transforms of ``--rgan_diffaug`` are gated per sample with a probability p (one more draw, the
 gates, after each draw of the transforms' uniforms); under adaptation every D step's outputs move
 p (augment.AdaptiveP), the log line ends with ``ada_p: ... r: ...`` and checkpoints gain the
-key ``ada``.  With ``--rgan_lecam`` the LeCam term (losses.lecam) joins the backward
+key ``ada``.  With ``xflip``, ``rot90`` or ``warp`` in ``--rgan_diffaug`` the uniforms of those
+geometric groups are one more draw, the last of the three.  With ``--rgan_lecam`` the LeCam term (losses.lecam) joins the backward
 that carries errD -- no further pass of D --, every D step moves its anchors (lecam.LeCam), the
 log line ends with ``lecam: ... a_real: ... a_fake: ...`` and checkpoints gain the key ``lecam``.
 """
@@ -207,7 +208,9 @@ class Trainer:
         for the global batch (group k = rows [k*batch_size, (k+1)*batch_size)), each group
         sharded like ``_uniform``.  With gating on, the [groups*B][4] gates come with them
         (feed key ``gate_D`` / ``gate_G``), drawn directly after from the same generator and
-        sharded the same way; None otherwise."""
+        sharded the same way; None otherwise.  With a geometric group in the policy, the
+        [groups*B][8] uniforms of those groups come last (feed key ``geo_D`` / ``geo_G``), drawn
+        after the gates and sharded the same way; None otherwise, and then nothing is drawn."""
         n = self.p.batch_size
 
         def rows(key, draw):
@@ -219,26 +222,28 @@ class Trainer:
             return t.to(self.device, non_blocking=True)
 
         u = rows(key, augment.draw)
-        return u, (rows("gate" + key[3:], augment.draw_gates) if self.ada is not None else None)
+        gate = rows("gate" + key[3:], augment.draw_gates) if self.ada is not None else None
+        return u, gate, (rows("geo" + key[3:], augment.draw_geo) if self.aug & augment.GEO else None)
 
-    def _augment(self, x, u, gate, rows=None, out=None):
-        """T(x) with the given rows of u (and of the gates, under the current p, when gating is on)."""
+    def _augment(self, x, u, gate, geo, rows=None, out=None):
+        """T(x) with the given rows of u (of the gates, under the current p, when gating is on,
+        and of the geometric groups' uniforms when the policy has one)."""
         if rows is not None:
-            u, gate = u[rows], (None if gate is None else gate[rows])
+            u, gate, geo = u[rows], (None if gate is None else gate[rows]), (None if geo is None else geo[rows])
         if gate is None:
-            return augment.apply(x, u, self.aug, out=out)
-        return augment.apply(x, u, self.aug, out=out, gate=gate, p=self.ada.p)
+            return augment.apply(x, u, self.aug, out=out, geo=geo)
+        return augment.apply(x, u, self.aug, out=out, gate=gate, p=self.ada.p, geo=geo)
 
-    def _augment_pair(self, a, b, u, gate, raw, out):
+    def _augment_pair(self, a, b, u, gate, geo, raw, out):
         """T(a), T(b) with u's two row groups, written back to back into ``out``: one call over
         both when a and b already lie back to back in ``raw``.  a may carry autograd."""
         B = self.B
         if (raw is not None and not a.requires_grad and a.data_ptr() == raw.data_ptr()
                 and b.data_ptr() == raw[B:].data_ptr()):
-            self._augment(raw, u, gate, out=out)
+            self._augment(raw, u, gate, geo, out=out)
             return out[:B], out[B:]
-        return (self._augment(a, u, gate, slice(0, B), out=out[:B]),
-                self._augment(b, u, gate, slice(B, None), out=out[B:]))
+        return (self._augment(a, u, gate, geo, slice(0, B), out=out[:B]),
+                self._augment(b, u, gate, geo, slice(B, None), out=out[B:]))
 
     def _generate_D(self, z, out=None):
         """The D step's fake batch.  Single samples: G(z) without a graph (GLI copies it into
@@ -303,13 +308,13 @@ class Trainer:
             # the pair D reads (same layout); x_raw is the untransformed batch of the record
             raw = torch.empty_like(pair) if pair is not None and self.aug else pair
             x = x_raw = self._real(feed, "x_D", out=raw[:self.B] if raw is not None else None)
-            z = u_aug = gate = None
+            z = u_aug = gate = geo = None
             if self.aug and not self.batch_D:
                 # the separate passes run D(x) before G(z): draw z now, so the draws come in the
                 # batched path's order (x, z, augmentation) whichever path runs
                 z = self._normal(feed, "z_D", zshape)
-                u_aug, gate = self._aug_u(feed, "aug_D", 2)
-                x = self._augment(x, u_aug, gate, slice(0, self.B))
+                u_aug, gate, geo = self._aug_u(feed, "aug_D", 2)
+                x = self._augment(x, u_aug, gate, geo, slice(0, self.B))
             if self.batch_D:
                 # D(x) and D(x_fake) as one batched pass (per-call BN statistics kept):
                 # the draws keep the reference's order (x, then z); D(x) does not read G
@@ -317,8 +322,8 @@ class Trainer:
                 self.flush()
                 x_fake = self._generate_D(z, out=raw[self.B:] if raw is not None else None)
                 if self.aug:
-                    u_aug, gate = self._aug_u(feed, "aug_D", 2)
-                    x, x_fake = self._augment_pair(x, x_fake, u_aug, gate, raw, pair)
+                    u_aug, gate, geo = self._aug_u(feed, "aug_D", 2)
+                    x, x_fake = self._augment_pair(x, x_fake, u_aug, gate, geo, raw, pair)
                 laid_out = (pair is not None and x.data_ptr() == pair.data_ptr()
                             and x_fake.data_ptr() == pair[self.B:].data_ptr())
                 y_all = D.forward_pair(x, x_fake, cat=pair if laid_out else None)
@@ -342,7 +347,7 @@ class Trainer:
                 self.flush()
                 x_fake = self._generate_D(z)
                 if self.aug:
-                    x_fake = self._augment(x_fake, u_aug, gate, slice(self.B, None))
+                    x_fake = self._augment(x_fake, u_aug, gate, geo, slice(self.B, None))
                 y_pred_fake = D(x_fake)
                 err_fake = loss_D_fake(kind, y_pred_fake)
                 lc = lecam(None, y_pred_fake, self.lecam) if self.lecam is not None else None
@@ -359,7 +364,7 @@ class Trainer:
                 self.flush()
                 x_fake = self._generate_D(z)
                 if self.aug:
-                    x_fake = self._augment(x_fake, u_aug, gate, slice(self.B, None))
+                    x_fake = self._augment(x_fake, u_aug, gate, geo, slice(self.B, None))
                 y_pred_fake = D(x_fake)
                 errD = loss_D(kind, y_pred, y_pred_fake)
                 lc = lecam(y_pred, y_pred_fake, self.lecam) if self.lecam is not None else None
@@ -375,6 +380,8 @@ class Trainer:
             if self.ada is not None:
                 rec.update(gate=gate)
                 self.ada.update(rec["y_pred"], rec["y_pred_fake"])  # (nothing without --rgan_ada_target)
+            if geo is not None:
+                rec.update(geo=geo)
             if gp_on:
                 # with augmentation on, x and x_fake are the transformed batches: what D saw
                 u = self._uniform(feed, "u", (p.batch_size, 1, 1, 1))
@@ -429,8 +436,8 @@ class Trainer:
                 x = x_raw = self._real(feed, "x_G", out=None if self.aug else pair_G[self.B:])
                 if self.aug:
                     # T(G(z)) carries autograd back into G; fake first, then real (the BN call order)
-                    u_aug, gate = self._aug_u(feed, "aug_G", 2)
-                    fake, x = self._augment_pair(fake, x, u_aug, gate, None, pair_G)
+                    u_aug, gate, geo = self._aug_u(feed, "aug_G", 2)
+                    fake, x = self._augment_pair(fake, x, u_aug, gate, geo, None, pair_G)
                     recG.update(aug=u_aug)
                 laid_out = (fake.data_ptr() == pair_G.data_ptr()
                             and x.data_ptr() == pair_G[self.B:].data_ptr())
@@ -444,8 +451,8 @@ class Trainer:
                     # the draws keep the batched path's order: z, the real batch, augmentation
                     if kind > 4:
                         x = self._real(feed, "x_G")
-                    u_aug, gate = self._aug_u(feed, "aug_G", 2 if kind > 4 else 1)
-                    fake = self._augment(fake, u_aug, gate, slice(0, self.B))
+                    u_aug, gate, geo = self._aug_u(feed, "aug_G", 2 if kind > 4 else 1)
+                    fake = self._augment(fake, u_aug, gate, geo, slice(0, self.B))
                     recG.update(aug=u_aug)
                 y_pred_fake = D(fake)
                 y_pred = None
@@ -453,11 +460,13 @@ class Trainer:
                     if x is None:
                         x = self._real(feed, "x_G")
                     with torch.no_grad():
-                        y_pred = D(self._augment(x, u_aug, gate, slice(self.B, None)) if self.aug else x)
+                        y_pred = D(self._augment(x, u_aug, gate, geo, slice(self.B, None)) if self.aug else x)
                     recG.update(x=x, y_pred=y_pred)
                 errG = loss_G(kind, y_pred_fake, y_pred)
             if self.ada is not None:
                 recG.update(gate=gate)
+            if self.aug & augment.GEO:
+                recG.update(geo=geo)
             self._arm(self.redG)
             self._backward(errG)
             recG.update(y_pred_fake=y_pred_fake.detach(), errG=errG.detach())
