@@ -18,11 +18,14 @@ ARCH = os.environ.get("RGAN_ARCH", "gfx950")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-I" + os.path.join(ROOT, "include"),
          "-Wno-unused-result", "-munsafe-fp-atomics"]
-# by measured compile time, slowest first (the first four within a few seconds of each other, then
-# about half, then <= 6 s each; the pool below starts them in this order)
-SOURCES = ["gemm_wgrad.hip", "gemm_conv.hip", "gemm_convt2.hip", "conv_gemm.hip", "bn_act.hip", "first_layer.hip",
-           "heads_optim.hip", "images.hip", "augment.hip", "ema.hip", "sampling.hip", "patches.hip", "upsample.hip",
-           "gp_zc.hip", "ada.hip", "lecam.hip", "augment_geo.hip"]
+# by measured compile time, slowest first (one at a time: gemm_wgrad 28 s, gemm_conv and conv_narrow 23 s,
+# gemm_convt2 21 s, bn_act 12 s, then augment_geo, first_layer, conv_pack, conv_reduce and heads_optim at
+# 3-5 s and the rest, the host-only conv_gemm / conv_plan / conv_prof among them, under 2 s each; the pool
+# below starts them in this order)
+SOURCES = ["gemm_wgrad.hip", "gemm_conv.hip", "conv_narrow.hip", "gemm_convt2.hip", "bn_act.hip", "augment_geo.hip",
+           "first_layer.hip", "conv_pack.hip", "conv_reduce.hip", "heads_optim.hip", "conv_gemm.hip", "conv_plan.hip",
+           "conv_prof.hip", "images.hip", "augment.hip", "ema.hip", "sampling.hip", "patches.hip", "upsample.hip",
+           "gp_zc.hip", "ada.hip", "lecam.hip"]
 
 
 def _stale(obj, src):

@@ -1,6 +1,6 @@
-// Types, constants and cross-unit declarations shared by the convolution units: gemm_body.h with
-// gemm_conv.hip / gemm_convt2.hip / gemm_wgrad.hip (the implicit-GEMM kernels) and conv_gemm.hip
-// (everything around them).  Host functions that cross units are declared here, once.
+// Types, constants and declarations shared by the implicit-GEMM kernels (gemm_body.h with
+// gemm_conv.hip / gemm_convt2.hip / gemm_wgrad.hip) and the units around them, which add their own
+// in conv_plan.h.  Host functions that cross into the GEMM units are declared here, once.
 #pragma once
 #include "common.h"
 
@@ -102,7 +102,7 @@ struct GemmArgs {
 
 enum { CFG_L = 0, CFG_M = 1, CFG_N = 2, CFG_S = 3 };
 
-// one GEMM launch as the planner chose it (conv_gemm.hip: Plan)
+// one GEMM launch as the planner chose it (conv_plan.h: Plan)
 struct GemmLaunch {
   const GemmArgs& g;
   int cfg;  // CFG_*
@@ -111,9 +111,9 @@ struct GemmLaunch {
   hipStream_t s;
 };
 
-// conv_gemm.hip
+// conv_plan.hip
 bool emu_bf16x6();  // opt-in fp32-on-bf16x6 GEMMs (rgan_set_gemm_emulation)
-// the launch profiler: the function that launches a kernel names it (printf-style, the demangled
+// the launch profiler (conv_prof.hip): the function that launches a kernel names it (printf-style, the demangled
 // symbol that bench.py and profiles/*_pmc_traffic.json key on); does nothing while no launch is
 // being recorded
 void prof_kernel(const char* fmt, ...) __attribute__((format(printf, 1, 2)));

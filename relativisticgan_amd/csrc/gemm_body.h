@@ -22,7 +22,7 @@
 //
 // This header holds the kernel template and its launcher.  gemm_conv.hip, gemm_convt2.hip and
 // gemm_wgrad.hip instantiate one GEMM mode each (three compile jobs instead of one); the split-K
-// reduces, the planner and everything else around the GEMM are in conv_gemm.hip.
+// reduces are in conv_reduce.hip, the planner in conv_plan.hip, run_plan in conv_gemm.hip.
 #pragma once
 #include "conv_types.h"
 

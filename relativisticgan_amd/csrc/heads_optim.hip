@@ -828,7 +828,7 @@ struct AdamBatch {
 };
 
 __global__ void adam_step_inc(float* step) { step[0] += 1.f; }
-extern "C" int rgan_adam_step_inc(float* step, void* stream) {  // (rgan_adam_packed, conv_gemm.hip)
+extern "C" int rgan_adam_step_inc(float* step, void* stream) {  // (rgan_adam_packed, conv_pack.hip)
   RGAN_REQUIRE(step);
   adam_step_inc<<<1, 1, 0, (hipStream_t)stream>>>(step);
   RGAN_CHECK_LAUNCH();

@@ -92,7 +92,7 @@ def test_conv_fwd_dgrad_wgrad_small(K, case, layout):
                                   (32, 128, 64, 8, 4, 2, 1, True)])
 def test_small_gemm_tiles(K, case):
     """Arch 1's small GEMMs (< 4 GFLOP that would split K 4+ ways on 128x128 tiles, or with
-    N <= 64) run on smaller tiles with fewer splits (conv_gemm.hip choose_tiling): the forward
+    N <= 64) run on smaller tiles with fewer splits (conv_plan.hip choose_tiling): the forward
     and data gradient on 64x64 tiles, the weight gradient on 128x64 (64x64 for <= 64 output
     channels) -- vs torch fp64, and those kernels are the ones that ran."""
     B, cin, cout, H, k, s, p, tr = case
@@ -124,7 +124,7 @@ def test_small_gemm_tiles(K, case):
 
 
 # family: (op, (B, cin, cout, H, k, s, p, transposed), x layout, the name the launch profiler reports).
-# The shapes are the smallest that meet the planners' conditions (conv_gemm.hip):
+# The shapes are the smallest that meet the planners' conditions (conv_plan.hip):
 #   plan_narrow_t     k4 s2 p1 ConvT, <= 4 outputs, NHWC input with C % 4 == 0
 #   plan_narrow_in    k4 Conv, <= 4 inputs; conv_img_in when also s2 p1, cout % 128 == 0, NHWC output,
 #                     wout == 16 (or % 32 == 0) and W-contiguous input rows (NCHW x, W % 4 == 0);

@@ -55,7 +55,8 @@ def main():
             touched.update(os.environ.get("VARIANT_SRC", ",".join(GEMM_UNITS)).split(","))
             if "VARIANT_SRC" not in os.environ:
                 print(f"note: {' '.join(defs)} reaches only {', '.join(GEMM_UNITS)}; a switch read by another "
-                      "unit (conv_gemm.hip: reduces, narrow, pack kernels) needs VARIANT_SRC=<units>", file=sys.stderr)
+                      "unit (conv_reduce.hip, conv_narrow.hip, conv_pack.hip: reduces, narrow, pack kernels; "
+                      "conv_plan.hip: the planner) needs VARIANT_SRC=<units>", file=sys.stderr)
         unknown = touched - set(B.SOURCES)
         if unknown:
             sys.exit(f"not a translation unit of the build: {sorted(unknown)}")
