@@ -79,7 +79,9 @@ int rgan_conv_pack_batch(int n, const RganConv* const* d, const int* which, cons
  * following activation when no BatchNorm sits between them.  wpacked: nullable
  * rgan_conv_pack(which=0) output (then w may be NULL).  wscale: nullable device scalar
  * (spectral norm's 1/sigma, torch/nn/utils/spectral_norm.py:115-116), applied to the
- * accumulator in the epilogue. */
+ * accumulator in the epilogue.  A stride-1 pad-0 ConvTranspose2d over a 1x1 map (the 1x1 -> k x k
+ * expansion) takes no bias: with one, rgan_conv_fwd and rgan_conv_fwd_bn return RGAN_EINVAL before
+ * any launch (rgan_conv_workspace cannot say so: it does not see the bias). */
 int rgan_conv_fwd(const RganConv* d, const float* x, const float* w, const float* wpacked,
                   const float* wscale, const float* bias, float* y, int act, float act_alpha,
                   void* ws, size_t ws_bytes, void* stream);

@@ -423,7 +423,10 @@ int plan_fwd(const RganConv* d, const float* x, const float* w, const float* wsc
     // ConvT weight [ci][co][kh][kw]
     set_pack(p, w, wscale, g.K, g.N, d->cin, 2, d->cout, 1, (long long)d->cout * 16, 16, 4, 1, 4, 4, 0, 1);
   } else if (d->hin == 1 && d->win == 1 && d->stride == 1 && d->pad == 0) {
-    // 1x1 -> kh x kw expansion (G's first layer, GLI:336): plain GEMM, N = (oh, ow, co)
+    // 1x1 -> kh x kw expansion (G's first layer, GLI:336): plain GEMM, N = (oh, ow, co).  Every epilogue
+    // and reduce reads bias[n], which is the output channel only where n = co: no bias here (the
+    // networks' expansions have none; tests/test_conv_edges_gpu.py)
+    if (bias) return RGAN_EINVAL;
     gemm_shape(p, MODE_CONV, 1, d->batch, KK * d->cout, d->cin, 1, 1, 1, 0, 1, 1, d->cin, 1);
     g.out = make_out(1, 1, 1, ys[0], 0, 0, d->kw, d->cout, ys[2], ys[3], ys[1]);
     // Wp[ci][(oh,ow,co)] = W[ci][co][oh][ow]

@@ -71,6 +71,13 @@ SPECIAL = [
 ]
 
 
+def _edges():
+    """The non-square maps and the geometries beyond the networks' three that tests/test_conv_edges_gpu.py runs
+    (tests/conv_ref.py: FAMILIES in both orientations, SIZE1, GEOMETRIES), as (..., transposed, win)."""
+    from tests import conv_ref
+    return [(c.B, c.cin, c.cout, c.H, c.k, c.s, c.p, c.tr, c.W) for c in conv_ref.all_cases()]
+
+
 def _strides(C, H, W, nchw):
     return (C * H * W, H * W, W, 1) if nchw else (H * W * C, 1, W * C, C)
 
@@ -82,19 +89,27 @@ def descriptors():
         shapes += [(b,) + l for l in _g0(size) + _d0(size) + _patch1x1(size) for b in (32, 2)]
     shapes += [(b,) + l for l in _arch1() for b in (32, 2)]
     shapes += SPECIAL
-    out, seen = [], set()
-    for B, cin, cout, hin, k, s, p, tr in shapes:
-        hout = (hin - 1) * s - 2 * p + k if tr else (hin + 2 * p - k) // s + 1
+    n_before = len(shapes)
+    shapes += _edges()
+    out, seen, first_edge = [], set(), None
+    for i, (B, cin, cout, hin, k, s, p, tr, *win) in enumerate(shapes):
+        if i == n_before:
+            first_edge = len(out)
+        win = win[0] if win else hin  # optional: square maps unless given
+        hout, wout = ((n - 1) * s - 2 * p + k if tr else (n + 2 * p - k) // s + 1 for n in (hin, win))
         # the image-side tensor: the output of a transposed conv and of a conv down to <= 4 channels, else the input
         y_side = tr or (cout <= 4 and cin > 4)
         for layout in ("nhwc", "nchw"):
-            xs = _strides(cin, hin, hin, layout == "nchw" and not y_side)
-            ys = _strides(cout, hout, hout, layout == "nchw" and y_side)
-            name = f"b{B}_{'convt' if tr else 'conv'}_{cin}x{hin}_to_{cout}x{hout}_k{k}s{s}p{p}_{layout}"
+            xs = _strides(cin, hin, win, layout == "nchw" and not y_side)
+            ys = _strides(cout, hout, wout, layout == "nchw" and y_side)
+            hw_in, hw_out = (f"{hin}", f"{hout}") if win == hin else (f"{hin}x{win}", f"{hout}x{wout}")
+            name = f"b{B}_{'convt' if tr else 'conv'}_{cin}x{hw_in}_to_{cout}x{hw_out}_k{k}s{s}p{p}_{layout}"
             if name not in seen:
                 seen.add(name)
-                out.append((name, (B, cin, hin, hin, cout, hout, hout, k, s, p, int(tr), xs, ys)))
-    return out
+                out.append((name, (B, cin, hin, win, cout, hout, wout, k, s, p, int(tr), xs, ys)))
+    # the edge rows go in front of the last earlier row: the fixture's last line carries no comma, so rows
+    # added behind it would also change it (a fixture diff of added lines only)
+    return out[:first_edge - 1] + out[first_edge:] + out[first_edge - 1:first_edge]
 
 
 def record():

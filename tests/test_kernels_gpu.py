@@ -3,6 +3,11 @@
 GPU-only (marked ``gpu``).  References are torch fp64 on the CPU for small shapes and
 torch fp32 on the device (MIOpen/ATen) for the full-size layer shapes of BASELINE's
 configs.  Tolerances are stated per test (fp32 accumulation over K terms).
+
+The conv tests here use square maps, dense 16-byte-aligned tensors and a relative L2 error.  Non-square
+maps, strided and 4-byte-aligned views, the geometries beyond k4 s2 p1 / k3 s1 / k4 s1 p0 / k1, unaligned
+gradient slices and an element-by-element bound: tests/test_conv_edges_gpu.py (reference and case tables in
+tests/conv_ref.py).
 """
 import math
 
