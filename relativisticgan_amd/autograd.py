@@ -238,55 +238,17 @@ class ConvLayerFn(torch.autograd.Function):
         # bufs = (running_mean, running_var, num_batches_tracked, training)
         # sn   = (u, v, inv_sigma) clones for spectral layers, else None
         wscale = sn[2] if spec.spectral else None
-        stats_eval = None
-        g1 = False
+        # G's first layer on its 1x1 input: conv + BatchNorm + act in one launch (and its own wgrad)
+        g1 = (spec.bn and bufs[3] and segs == 1 and bias is None and wscale is None and not dp.sync_bn()
+              and K.g1_ok(x, w, spec.geom))
         if spec.bn:
-            rm, rv, nbt, training = bufs
-            g1 = (training and segs == 1 and bias is None and wscale is None and not dp.sync_bn()
-                  and K.g1_ok(x, w, spec.geom))
-            if g1:
-                # G's first layer on its 1x1 input: conv + BatchNorm + act in one launch
-                y, a, stats = K.g1_fwd_bn(x, w, gamma, beta, spec.eps, spec.momentum, rm, rv, nbt, spec.act,
-                                          spec.alpha, out=out)
-                part, S = None, 0
-            elif training:
-                y, part, S = K.conv_fwd_bn(x, w, spec.geom, bias=bias, wscale=wscale, cache=True, segs=segs)
-            else:
-                y, part, S = K.conv_fwd(x, w, spec.geom, bias=bias, wscale=wscale, cache=True), None, 0
-            C = y.shape[1]
-            # statistics from the epilogue's segment sums + normalisation in one call (one
-            # launch for small layers): one process / per-shard BN, dense aligned NHWC
-            seg_fused = (training and part is not None and segs <= 2 and S % segs == 0 and not dp.sync_bn()
-                         and K.is_nhwc(y) and y.data_ptr() % 16 == 0 and C % 4 == 0
-                         and (out is None or (K.is_nhwc(out) and out.data_ptr() % 16 == 0)))
-            if g1:
-                pass
-            elif seg_fused:
-                a = torch.empty_like(y) if out is None else out
-                stats = torch.empty((segs, 2 * C) if segs > 1 else (2 * C,), dtype=torch.float32, device=y.device)
-                K.bn_segment_apply(part, S, y, spec.eps, spec.momentum, rm, rv, nbt, gamma, beta, spec.act,
-                                   spec.alpha, stats.view(segs, 2 * C), a)
-            elif training and segs > 1:
-                Bs = y.shape[0] // segs
-                a = torch.empty_like(y) if out is None else out
-                stats = torch.empty((segs, 2 * C), dtype=torch.float32, device=y.device)
-                for s_ in range(segs):
-                    sl = slice(s_ * Bs, (s_ + 1) * Bs)
-                    seg = (part, s_ * S // segs, (s_ + 1) * S // segs) if part is not None else None
-                    _train_stats(y[sl], spec, rm, rv, nbt, seg, out=stats[s_])
-                    K.bn_apply(y[sl], stats[s_], gamma, beta, spec.act, spec.alpha, out=a[sl])
-            else:
-                if training:
-                    stats = _train_stats(y, spec, rm, rv, nbt, (part, 0, S) if part is not None else None)
-                else:
-                    stats = torch.cat([rm, torch.rsqrt(rv + spec.eps)])
-                    stats_eval = (rm, stats[C:])
-                a = K.bn_apply(y, stats, gamma, beta, spec.act, spec.alpha, out=out)
-            ctx.save_for_backward(x, w, bias, gamma, beta, y, stats, *(sn if spec.spectral else ()))
+            y, a, stats, stats_eval = ConvLayerFn._bn_forward(x, w, bias, gamma, beta, spec, bufs, wscale, segs,
+                                                              out, g1)
         else:
+            y = stats = stats_eval = None
             a = K.conv_fwd(x, w, spec.geom, bias=bias, act=spec.act, alpha=spec.alpha, wscale=wscale,
                            nchw_out=spec.nchw_out, cache=True, out=out)
-            ctx.save_for_backward(x, w, bias, gamma, beta, a, None, *(sn if spec.spectral else ()))
+        ctx.save_for_backward(x, w, bias, gamma, beta, y if spec.bn else a, stats, *(sn if spec.spectral else ()))
         if ACT_TRACE is not None and spec.act in _KINKED:
             ACT_TRACE.append((a.detach() > 0).cpu())
             ACT_TAGS.append(TRACE_NET)
@@ -311,21 +273,54 @@ class ConvLayerFn(torch.autograd.Function):
         return a
 
     @staticmethod
+    def _bn_forward(x, w, bias, gamma, beta, spec, bufs, wscale, segs, out, g1):
+        """(y, a, stats, stats_eval) of a BatchNorm layer: the conv output, the layer output,
+        (mean, invstd) as float[2C] ([segs][2C] of a segmented call) and, in eval mode, the
+        running (mean, invstd) the composite backward normalises with."""
+        rm, rv, nbt, training = bufs
+        if g1:
+            return K.g1_fwd_bn(x, w, gamma, beta, spec.eps, spec.momentum, rm, rv, nbt, spec.act, spec.alpha,
+                               out=out) + (None,)
+        if training:
+            y, part, S = K.conv_fwd_bn(x, w, spec.geom, bias=bias, wscale=wscale, cache=True, segs=segs)
+        else:
+            y, part, S = K.conv_fwd(x, w, spec.geom, bias=bias, wscale=wscale, cache=True), None, 0
+        C = y.shape[1]
+        if (training and part is not None and segs <= 2 and S % segs == 0 and not dp.sync_bn()
+                and K.is_nhwc(y) and y.data_ptr() % 16 == 0 and C % 4 == 0
+                and (out is None or (K.is_nhwc(out) and out.data_ptr() % 16 == 0))):
+            # statistics from the epilogue's segment sums + normalisation in one call (one
+            # launch for small layers): one process / per-shard BN, dense aligned NHWC
+            a = torch.empty_like(y) if out is None else out
+            stats = torch.empty((segs, 2 * C) if segs > 1 else (2 * C,), dtype=torch.float32, device=y.device)
+            K.bn_segment_apply(part, S, y, spec.eps, spec.momentum, rm, rv, nbt, gamma, beta, spec.act,
+                               spec.alpha, stats.view(segs, 2 * C), a)
+            return y, a, stats, None
+        if training and segs > 1:
+            Bs = y.shape[0] // segs
+            a = torch.empty_like(y) if out is None else out
+            stats = torch.empty((segs, 2 * C), dtype=torch.float32, device=y.device)
+            for s_ in range(segs):
+                sl = slice(s_ * Bs, (s_ + 1) * Bs)
+                seg = (part, s_ * S // segs, (s_ + 1) * S // segs) if part is not None else None
+                _train_stats(y[sl], spec, rm, rv, nbt, seg, out=stats[s_])
+                K.bn_apply(y[sl], stats[s_], gamma, beta, spec.act, spec.alpha, out=a[sl])
+            return y, a, stats, None
+        if training:
+            stats, stats_eval = _train_stats(y, spec, rm, rv, nbt, (part, 0, S) if part is not None else None), None
+        else:
+            stats = torch.cat([rm, torch.rsqrt(rv + spec.eps)])
+            stats_eval = (rm, stats[C:])
+        return y, K.bn_apply(y, stats, gamma, beta, spec.act, spec.alpha, out=out), stats, stats_eval
+
+    @staticmethod
     def backward(ctx, da):
         spec = ctx.spec
         saved = ctx.saved_tensors
-        x, w, bias, gamma, beta, t5, stats = saved[:7]
+        x, w, bias, gamma, beta, t5, stats = saved[:7]  # t5: the conv output y (BatchNorm) or the layer output a
         sn = saved[7:10] if spec.spectral else None
-        nx, nw, nb, ng, nbeta = ctx.needs_input_grad[:5]
+        nx = ctx.needs_input_grad[0]
         if torch.is_grad_enabled():
-            if ctx.segs > 1:
-                raise NotImplementedError("double backward through a segmented (batched) layer call")
-            # the graph this builds reads the layer's activations: a later backward through the
-            # forward nodes sums its gradients with the chain's, so the chain's hand-offs
-            # (LayerLink: one consumer per output) are off for this call
-            for lk in (ctx.link_in, ctx.link_out):
-                if lk is not None:
-                    lk.mode, lk.done = 0, None
             return ConvLayerFn._create_graph_backward(ctx, da, x, w, bias, gamma, beta, sn)
         dx_full = dx_out = None
         Bg = x.shape[0]
@@ -343,128 +338,165 @@ class ConvLayerFn(torch.autograd.Function):
                 dx_out = dx_full[:Bg]
                 if torch.is_anomaly_enabled():
                     dx_full[Bg:].zero_()
-        # this layer's output gradient may arrive with its first backward pass already applied
-        # by the layer above (LayerLink): g = da * act' (+ BN sums), or da * act'
-        done = ctx.link_out.done if ctx.link_out is not None else None
-        if done is not None:
-            ctx.link_out.done = None
-            if not done[1].fused:
-                done = None  # the GEMM above wrote the plain gradient
-            elif done[0] != da.data_ptr():
-                # the layer above applied this layer's act' / BatchNorm sums to the gradient it
-                # produced, but a different tensor arrived here.  Links exist only between
-                # consecutive layers inside one nets._Net call, whose intermediate activations
-                # never leave the call (no user hook or second consumer can reach them), so this
-                # is an internal assertion: running the first pass again would be silently wrong
-                raise RuntimeError("LayerLink: the fused output gradient was replaced before this layer's "
-                                   "backward (hook / cast / second consumer of the activation)")
-        # ... and this layer's data gradient may carry the layer below's first pass
+        done = ConvLayerFn._handed_down(ctx, da)
+        # this layer's data gradient may carry the layer below's first pass
         # (the two layers ran in one chain call: same batch segments, same gradient rows)
         post = ctx.link_in.post(Bg, ctx.gsegs) if nx and ctx.link_in is not None else None
-        wscale = sn[2] if spec.spectral else None
-        dgamma = dbeta = None
-        if spec.bn:
-            y = t5
-            P = y.shape[0] * y.shape[2] * y.shape[3]
-            if ctx.stats_eval is not None:
-                # the reference never calls .eval() (GLI:560-714): no training path reaches this
-                raise NotImplementedError("backward through eval-mode BatchNorm is not on the training path")
-            if done is not None and done[1].mode == 2:
-                # da is g = da * act' and the sums are in done[1].part (the layer above's GEMM)
-                dy, dgamma, dbeta = K.bn_backward_parts(da, y, stats, gamma, beta, done[1], ng, nbeta)
-            elif stats.dim() == 2:  # segmented call: BN backward per segment, one dy
-                dy, dgamma, dbeta = ConvLayerFn._seg_bn_backward(ctx, da, y, stats, gamma, beta, ng, nbeta)
-            elif dp.sync_bn():
-                sums, da_c = K.bn_backward_sums(da, y, stats, gamma, beta, spec.act, spec.alpha)
-                # dgamma/dbeta stay shard-local (from the pre-all-reduce sums): the bucketed
-                # gradient all-reduce sums them like every other parameter gradient
-                C = y.shape[1]
-                dgamma = torch.empty(C, dtype=torch.float32, device=y.device) if ng and gamma is not None else None
-                dbeta = torch.empty(C, dtype=torch.float32, device=y.device) if nbeta and beta is not None else None
-                K.bn_affine_grads(sums, stats, C, dgamma, dbeta)
-                dp.all_reduce_sum(sums)
-                dy, _, _ = K.bn_backward_apply(da_c, y, stats, gamma, beta, spec.act, spec.alpha, sums,
-                                               P * dp.world(), need_affine=False)
-            else:
-                dy, dgamma, dbeta = K.bn_backward(da, y, stats, gamma, beta, spec.act, spec.alpha,
-                                                  need_affine=ng or nbeta)
-        elif spec.act != "none" and not (done is not None and done[1].mode == 1):
-            dy = K.act_backward(da, t5, spec.act, spec.alpha)
-        else:
-            dy = da
-        if ConvLayerFn._patch_conv(spec, x):
-            # image-side Conv2d (D's first layer; the forward ran the direct narrow kernel):
-            # the weight gradient is a 1x1 GEMM over the image's patch matrix
-            dx = (K.conv_dgrad(dy, w, spec.geom, tuple(x.shape), wscale=wscale, out=dx_out, like=x, cache=True,
-                               post=post) if nx else None)
-            dw = db = None
-            if nw or nb:
-                g1, db = K.conv_wgrad(K.patches_k4s2(x), dy, K.G1X1, (w.shape[0], 64, 1, 1),
-                                      with_bias=bias is not None and nb)
-                dw = K.unpatch_grad(g1, w.shape[0], w.shape[1], 64, 1,
-                                    into=dp.grad_view(w) if nw and not spec.spectral else None)
-        elif ConvLayerFn._patch_convt(spec, w, bias):
-            # image-side ConvTranspose2d (G's last layer): both gradients are 1x1 GEMMs over
-            # the patch matrix of the image gradient, on x's grid
-            Xg = K.patches_k4s2(dy)
-            dx = (K.conv_fwd(Xg, K.PATCHW.get(w, True), K.G1X1, wscale=wscale, out=dx_out, cache=True, post=post)
-                  if nx else None)
-            dw = db = None
-            if nw:
-                g1, _ = K.conv_wgrad(Xg, x, K.G1X1, (w.shape[0], 64, 1, 1))
-                dw = K.unpatch_grad(g1, w.shape[0], w.shape[1], 64, 1,
-                                    into=dp.grad_view(w) if not spec.spectral else None)
-        else:
-            dx = (K.conv_dgrad(dy, w, spec.geom, tuple(x.shape), wscale=wscale, out=dx_out, like=x, cache=True,
-                               post=post) if nx else None)
-            dw = db = None
-            if nw and not nb and spec.geom.upsample == 1 and ConvLayerFn._own_grad(w, bias):
-                # The weight gradient goes straight into w.grad: set when it is empty (what
-                # AccumulateGrad would do), added in the GEMM epilogue / sigma correction when
-                # an earlier call of the net left one (spectral D's separate D(x) / D(G(z))
-                # calls, heads 1-4's two backwards) -- instead of autograd summing the calls'
-                # gradients with an add kernel (same values: grad + dw, one rounding).  No
-                # gradient is returned for w.
-                acc = w.grad
-                if spec.spectral:
-                    u, v, inv_sigma = sn
-                    dwe, _ = K.conv_wgrad(x, dy, spec.geom, tuple(w.shape))
-                    g = K.spectral_backward(w, dwe, u, v, inv_sigma, spec.geom.transposed, out=acc)
-                elif ctx.g1:
-                    g = K.g1_wgrad(x, dy, tuple(w.shape), out=acc)
-                else:
-                    g, _ = K.conv_wgrad(x, dy, spec.geom, tuple(w.shape), out=acc)
-                if acc is None:
-                    w.grad = g
-                ConvLayerFn._hand_down(ctx, post, dx)
-                return ((dx if dx_full is None else dx_full), None, None, dgamma, dbeta, None, None, None, None, None,
-                        None, None, None)
-            if nw or nb:
-                # data parallel: the weight gradient lands in its gradient bucket's slice
-                # (dp.grad_view), which autograd then adopts as .grad (no bucket copy)
-                into = (dp.grad_view(w) if nw and not (bias is not None and nb) and not spec.spectral
-                        and spec.geom.upsample == 1 else None)
-                if ctx.g1 and nw:
-                    dw, db = K.g1_wgrad(x, dy, tuple(w.shape), into=into), None
-                else:
-                    dw, db = K.conv_wgrad(x, dy, spec.geom, tuple(w.shape), with_bias=bias is not None and nb,
-                                          into=into)
-        if nw or nb:
-            if spec.spectral and nw:
-                u, v, inv_sigma = sn
-                dw = K.spectral_backward(w, dw, u, v, inv_sigma, spec.geom.transposed)
-            if not nw:
-                dw = None
+        dy, dgamma, dbeta = ConvLayerFn._first_pass(ctx, da, t5, stats, gamma, beta, done)
+        # image-side ConvTranspose2d (G's last layer): both gradients are 1x1 GEMMs over the
+        # patch matrix of the image gradient, on x's grid
+        Xg = K.patches_k4s2(dy) if ConvLayerFn._patch_convt(spec, w, bias) else None
+        dx = ConvLayerFn._data_grad(spec, dy, x, w, sn, Xg, dx_out, post) if nx else None
+        dw, db = ConvLayerFn._weight_grad(ctx, dy, x, w, bias, sn, Xg)
         ConvLayerFn._hand_down(ctx, post, dx)
-        if dx_full is not None:
-            dx = dx_full
-        return dx, dw, db, dgamma, dbeta, None, None, None, None, None, None, None, None
+        return ConvLayerFn._grads(dx if dx_full is None else dx_full, dw, db, dgamma, dbeta)
+
+    @staticmethod
+    def _grads(*grads):
+        """backward's result: the gradients of x, w, bias, gamma, beta, then None for every
+        other input of forward."""
+        return grads + (None,) * (ConvLayerFn.forward.__code__.co_argcount - 1 - len(grads))
+
+    @staticmethod
+    def _handed_down(ctx, da):
+        """The kernels.Post that the layer above already applied to ``da`` (LayerLink: da is
+        g = da * act', for mode 2 with the BatchNorm sums in its ``part``), or None."""
+        done = ctx.link_out.done if ctx.link_out is not None else None
+        if done is None:
+            return None
+        ctx.link_out.done = None
+        if not done[1].fused:
+            return None  # the GEMM above wrote the plain gradient
+        if done[0] != da.data_ptr():
+            # the layer above applied this layer's act' / BatchNorm sums to the gradient it
+            # produced, but a different tensor arrived here.  Links exist only between
+            # consecutive layers inside one nets._Net call, whose intermediate activations
+            # never leave the call (no user hook or second consumer can reach them), so this
+            # is an internal assertion: running the first pass again would be silently wrong
+            raise RuntimeError("LayerLink: the fused output gradient was replaced before this layer's "
+                               "backward (hook / cast / second consumer of the activation)")
+        return done[1]
 
     @staticmethod
     def _hand_down(ctx, post, dx):
         """The layer below starts its backward from dx as the post-op left it (LayerLink)."""
         if post is not None and post.fused and dx is not None:
             ctx.link_in.done = (dx.data_ptr(), post)
+
+    @staticmethod
+    def _first_pass(ctx, da, t5, stats, gamma, beta, done):
+        """(dy, dgamma, dbeta): ``da`` through act' and the BatchNorm backward; ``done``: what of
+        it the layer above did (_handed_down)."""
+        spec = ctx.spec
+        ng, nbeta = ctx.needs_input_grad[3:5]
+        if not spec.bn:
+            if spec.act == "none" or (done is not None and done.mode == 1):
+                return da, None, None
+            return K.act_backward(da, t5, spec.act, spec.alpha), None, None
+        y = t5
+        if ctx.stats_eval is not None:
+            # the reference never calls .eval() (GLI:560-714): no training path reaches this
+            raise NotImplementedError("backward through eval-mode BatchNorm is not on the training path")
+        if done is not None and done.mode == 2:
+            return K.bn_backward_parts(da, y, stats, gamma, beta, done, ng, nbeta)
+        if stats.dim() == 2:  # segmented call: BN backward per segment, one dy
+            return ConvLayerFn._seg_bn_backward(ctx, da, y, stats, gamma, beta, ng, nbeta)
+        if not dp.sync_bn():
+            return K.bn_backward(da, y, stats, gamma, beta, spec.act, spec.alpha, need_affine=ng or nbeta)
+        sums, da_c = K.bn_backward_sums(da, y, stats, gamma, beta, spec.act, spec.alpha)
+        # dgamma/dbeta stay shard-local (from the pre-all-reduce sums): the bucketed
+        # gradient all-reduce sums them like every other parameter gradient
+        dgamma, dbeta = K.affine_grad_bufs(y, gamma, beta, ng, nbeta)
+        K.bn_affine_grads(sums, stats, y.shape[1], dgamma, dbeta)
+        dp.all_reduce_sum(sums)
+        dy, _, _ = K.bn_backward_apply(da_c, y, stats, gamma, beta, spec.act, spec.alpha, sums,
+                                       y.shape[0] * y.shape[2] * y.shape[3] * dp.world(), need_affine=False)
+        return dy, dgamma, dbeta
+
+    @staticmethod
+    def _seg_bn_backward(ctx, da, y, stats, gamma, beta, ng, nbeta):
+        spec = ctx.spec
+        da = K.as_nhwc(da)
+        dy = torch.empty_like(y)
+        Bs = y.shape[0] // ctx.segs
+        P = Bs * y.shape[2] * y.shape[3]
+        C = y.shape[1]
+        dgamma = dbeta = None
+        if (ctx.segs == 2 and not dp.sync_bn() and K.is_nhwc(y) and C % 4 == 0
+                and y.data_ptr() % 16 == 0 and da.data_ptr() % 16 == 0 and dy.data_ptr() % 16 == 0):
+            # both calls' BatchNorm backward in one set of launches (affine gradients summed)
+            return K.bn_backward_segments(da, y, stats, gamma, beta, spec.act, spec.alpha, ng, nbeta, dy)
+        if not dp.sync_bn():
+            dgamma, dbeta = K.affine_grad_bufs(y, gamma, beta, ng, nbeta)
+        for s_ in range(ctx.segs):
+            sl = slice(s_ * Bs, (s_ + 1) * Bs)
+            sums, da_c = K.bn_backward_sums(da[sl], y[sl], stats[s_], gamma, beta, spec.act, spec.alpha)
+            if dp.sync_bn():
+                dg = (sums[C:] * stats[s_, C:2 * C].double()).float() if ng and gamma is not None else None
+                db = sums[:C].float() if nbeta and beta is not None else None
+                dp.all_reduce_sum(sums)
+                K.bn_backward_apply(da_c, y[sl], stats[s_], gamma, beta, spec.act, spec.alpha, sums,
+                                    P * dp.world(), need_affine=False, out=dy[sl])
+                dgamma = dg if dgamma is None or dg is None else dgamma + dg
+                dbeta = db if dbeta is None or db is None else dbeta + db
+            else:
+                # the segments' affine gradients are summed in the apply kernel (segment 0
+                # writes, later segments add): no separate add pass
+                K.bn_backward_apply_ex(da_c, y[sl], stats[s_], gamma, beta, spec.act, spec.alpha, sums, P,
+                                       out=dy[sl], dgamma=dgamma, dbeta=dbeta, accumulate_affine=s_ > 0)
+        return dy, dgamma, dbeta
+
+    @staticmethod
+    def _data_grad(spec, dy, x, w, sn, Xg, dx_out, post):
+        """dx, with the layer below's first pass in the GEMM's epilogue where ``post`` asks."""
+        wscale = sn[2] if spec.spectral else None
+        if Xg is not None:
+            return K.conv_fwd(Xg, K.PATCHW.get(w, True), K.G1X1, wscale=wscale, out=dx_out, cache=True, post=post)
+        return K.conv_dgrad(dy, w, spec.geom, tuple(x.shape), wscale=wscale, out=dx_out, like=x, cache=True,
+                            post=post)
+
+    @staticmethod
+    def _weight_grad(ctx, dy, x, w, bias, sn, Xg):
+        """(dw, db) for autograd; (None, None) where the layer owns w.grad and wrote it."""
+        spec = ctx.spec
+        nw, nb = ctx.needs_input_grad[1:3]
+        if not (nw or nb):
+            return None, None
+        with_bias = bias is not None and nb
+        shape = tuple(w.shape)
+        # The weight gradient may go straight into w.grad: set when it is empty (what
+        # AccumulateGrad would do), added in the GEMM epilogue / sigma correction when an
+        # earlier call of the net left one (spectral D's separate D(x) / D(G(z)) calls, heads
+        # 1-4's two backwards) -- instead of autograd summing the calls' gradients with an add
+        # kernel (same values: grad + dw, one rounding).  No gradient is returned for w then.
+        own = acc = None
+        if ConvLayerFn._patch_conv(spec, x) or Xg is not None:
+            # image-side layers (the forwards ran the direct narrow kernels): a 1x1 GEMM over
+            # the patch matrix of the image (Conv2d) or of the image gradient (ConvTranspose2d)
+            X, Y = (K.patches_k4s2(x), dy) if Xg is None else (Xg, x)
+            g, db = K.conv_wgrad(X, Y, K.G1X1, (shape[0], 64, 1, 1), with_bias=with_bias)
+            dw = K.unpatch_grad(g, shape[0], shape[1], 64, 1,
+                                into=dp.grad_view(w) if nw and not spec.spectral else None)
+        else:
+            own = nw and not nb and spec.geom.upsample == 1 and ConvLayerFn._own_grad(w, bias)
+            acc = w.grad if own else None
+            # data parallel: the weight gradient lands in its gradient bucket's slice
+            # (dp.grad_view), which autograd then adopts as .grad (no bucket copy)
+            into = (dp.grad_view(w) if nw and not own and not with_bias and not spec.spectral
+                    and spec.geom.upsample == 1 else None)
+            if ctx.g1 and nw:
+                dw, db = K.g1_wgrad(x, dy, shape, out=acc, into=into), None
+            else:
+                dw, db = K.conv_wgrad(x, dy, spec.geom, shape, with_bias=with_bias,
+                                      out=None if spec.spectral else acc, into=into)
+        if spec.spectral and nw:
+            u, v, inv_sigma = sn
+            dw = K.spectral_backward(w, dw, u, v, inv_sigma, spec.geom.transposed, out=acc)
+        if own:
+            if acc is None:
+                w.grad = dw
+            return None, None
+        return (dw if nw else None), db
 
     @staticmethod
     def _own_grad(w, bias):
@@ -483,6 +515,7 @@ class ConvLayerFn(torch.autograd.Function):
 
     @staticmethod
     def _patch_conv(spec, x):
+        """Image-side Conv2d (D's first layer): its weight gradient runs over the patch matrix."""
         return (not spec.geom.transposed and not spec.bn and K.patchable(spec.geom, x.shape[1])
                 and x.shape[2] % 2 == 0 and x.shape[3] % 2 == 0)
 
@@ -492,56 +525,25 @@ class ConvLayerFn(torch.autograd.Function):
                 and K.patchable(spec.geom, w.shape[1]))
 
     @staticmethod
-    def _seg_bn_backward(ctx, da, y, stats, gamma, beta, ng, nbeta):
-        spec = ctx.spec
-        if not K.is_nhwc(da):
-            da = da.contiguous(memory_format=torch.channels_last)
-        dy = torch.empty_like(y)
-        Bs = y.shape[0] // ctx.segs
-        P = Bs * y.shape[2] * y.shape[3]
-        C = y.shape[1]
-        dgamma = dbeta = None
-        if (ctx.segs == 2 and not dp.sync_bn() and K.is_nhwc(y) and C % 4 == 0
-                and y.data_ptr() % 16 == 0 and da.data_ptr() % 16 == 0 and dy.data_ptr() % 16 == 0):
-            # both calls' BatchNorm backward in one set of launches (affine gradients summed)
-            return K.bn_backward_segments(da, y, stats, gamma, beta, spec.act, spec.alpha, ng, nbeta, dy)
-        for s_ in range(ctx.segs):
-            sl = slice(s_ * Bs, (s_ + 1) * Bs)
-            if dp.sync_bn():
-                sums, da_c = K.bn_backward_sums(da[sl], y[sl], stats[s_], gamma, beta, spec.act, spec.alpha)
-                dg = (sums[C:] * stats[s_, C:2 * C].double()).float() if ng and gamma is not None else None
-                db = sums[:C].float() if nbeta and beta is not None else None
-                dp.all_reduce_sum(sums)
-                K.bn_backward_apply(da_c, y[sl], stats[s_], gamma, beta, spec.act, spec.alpha, sums,
-                                    P * dp.world(), need_affine=False, out=dy[sl])
-                dgamma = dg if dgamma is None or dg is None else dgamma + dg
-                dbeta = db if dbeta is None or db is None else dbeta + db
-            else:
-                # the segments' affine gradients are summed in the apply kernel (segment 0
-                # writes, later segments add): no separate add pass
-                if s_ == 0:
-                    dgamma = torch.empty(C, dtype=torch.float32, device=y.device) if ng and gamma is not None else None
-                    dbeta = torch.empty(C, dtype=torch.float32, device=y.device) if nbeta and beta is not None else None
-                sums, da_c = K.bn_backward_sums(da[sl], y[sl], stats[s_], gamma, beta, spec.act, spec.alpha)
-                K.bn_backward_apply_ex(da_c, y[sl], stats[s_], gamma, beta, spec.act, spec.alpha, sums, P,
-                                       out=dy[sl], dgamma=dgamma, dbeta=dbeta, accumulate_affine=s_ > 0)
-        return dy, dgamma, dbeta
-
-    @staticmethod
     def _create_graph_backward(ctx, da, x, w, bias, gamma, beta, sn):
         """Differentiable backward: rebuild the layer from its REAL inputs (x keeps its
         history, w is the Parameter) and let autograd differentiate the composite, so the
         returned gradients are functions of (da, x, w, ...) that gp.backward() can follow."""
-        spec = ctx.spec
-        slots = [i for i, t in enumerate((x, w, bias, gamma, beta))
-                 if t is not None and ctx.needs_input_grad[i]]
-        out = [None] * 13
-        if not slots:
-            return tuple(out)
+        if ctx.segs > 1:
+            raise NotImplementedError("double backward through a segmented (batched) layer call")
+        # the graph this builds reads the layer's activations: a later backward through the
+        # forward nodes sums its gradients with the chain's, so the chain's hand-offs
+        # (LayerLink: one consumer per output) are off for this call
+        for lk in (ctx.link_in, ctx.link_out):
+            if lk is not None:
+                lk.mode, lk.done = 0, None
         src = (x, w, bias, gamma, beta)
-        with torch.enable_grad():
-            a = composite_layer(x, w, bias, gamma, beta, spec, ctx.stats_eval, sn)
-            grads = torch.autograd.grad(a, [src[i] for i in slots], da, create_graph=True, allow_unused=True)
-        for i, g in zip(slots, grads):
-            out[i] = g
-        return tuple(out)
+        slots = [i for i, t in enumerate(src) if t is not None and ctx.needs_input_grad[i]]
+        out = [None] * len(src)
+        if slots:
+            with torch.enable_grad():
+                a = composite_layer(x, w, bias, gamma, beta, ctx.spec, ctx.stats_eval, sn)
+                grads = torch.autograd.grad(a, [src[i] for i in slots], da, create_graph=True, allow_unused=True)
+            for i, g in zip(slots, grads):
+                out[i] = g
+        return ConvLayerFn._grads(*out)

@@ -60,6 +60,18 @@ def is_nhwc(t):
     return t.stride() == (H * W * C, 1, W * C, C) or (H == 1 and W == 1 and t.stride()[1] == 1)
 
 
+def as_nhwc(t):
+    return t if is_nhwc(t) else t.contiguous(memory_format=torch.channels_last)
+
+
+def affine_grad_bufs(y, gamma, beta, need_gamma, need_beta):
+    """(dgamma, dbeta) buffers of BatchNorm over y's channels; None where not asked for."""
+    C = y.shape[1]
+    dgamma = torch.empty(C, dtype=torch.float32, device=y.device) if need_gamma and gamma is not None else None
+    dbeta = torch.empty(C, dtype=torch.float32, device=y.device) if need_beta and beta is not None else None
+    return dgamma, dbeta
+
+
 def _desc(x_shape, x_stride, y_shape, y_stride, geom):
     d = L.RganConv()
     B, cin, hin, win = x_shape
@@ -80,38 +92,77 @@ def _f32(*ts):
             raise L.RganError(f"expected float32 tensors, got {t.dtype}")
 
 
-class _PackCache:
-    """GEMM-ready weight layouts, cached per (weight tensor, layout, version).
+class _Entry:
+    """One cached layout of a weight: ``ref`` the weight's base tensor (held weakly: a storage
+    address can be reused by a later tensor with the same version count), ``ver`` / ``ptr`` the
+    version and address of the weight ``buf`` was made from, and for a pack what makes it again:
+    the descriptor ``d``, the layout ``which`` and ``geo``, the packed view's (shape, stride,
+    offset) on its base, None for the base itself."""
 
-    Weights change only at optimizer steps (fused Adam bumps the autograd version
-    counter), while every net runs 2-4 times per iteration, so most conv launches reuse
-    a packed copy.  Entries are keyed by the weight's base tensor object (held weakly:
-    a storage address can be reused by a later tensor with the same version count) and
-    one buffer per (weight, layout) is refilled in place when the version moves."""
+    __slots__ = ("ref", "ver", "ptr", "buf", "d", "which", "geo")
+
+    def __init__(self, ref, ver, ptr, buf, d=None, which=None, geo=None):
+        self.ref, self.ver, self.ptr, self.buf, self.d, self.which, self.geo = ref, ver, ptr, buf, d, which, geo
+
+    def matches(self, w):
+        return self.ver == w._version and self.ptr == w.data_ptr()
+
+    def current(self, base, w):
+        """``buf`` holds the present values of ``w``, a view of (or) ``base``."""
+        return self.ref() is base and self.matches(w)
+
+    def mark(self, w):
+        """``buf`` was rewritten from ``w``'s present values."""
+        self.ver, self.ptr = w._version, w.data_ptr()
+
+
+class _WeightCache:
+    """{key: _Entry}; an entry goes when its weight's base is collected."""
 
     def __init__(self):
         self.entries = {}
 
+    def _put(self, key, base, w, buf, d=None, which=None, geo=None):
+        self.entries[key] = _Entry(weakref.ref(base, self._drop(key)), w._version, w.data_ptr(), buf, d, which, geo)
+
+    def _drop(self, key):
+        def cb(_ref):
+            ent = self.entries.get(key)
+            if ent is not None and ent.ref is _ref:
+                del self.entries[key]
+        return cb
+
+    def clear(self):
+        self.entries.clear()
+
+
+class _PackCache(_WeightCache):
+    """GEMM-ready weight layouts, cached per (weight tensor, layout, version).
+
+    Weights change only at optimizer steps (fused Adam bumps the autograd version
+    counter), while every net runs 2-4 times per iteration, so most conv launches reuse
+    a packed copy.  Entries are keyed by the weight's base tensor object and
+    one buffer per (weight, layout) is refilled in place when the version moves."""
+
     def get(self, w, which, geom, d):
         base = w._base if w._base is not None else w
         key = (id(base), which, geom, d.cin, d.cout, d.hin, d.win, d.hout, d.wout)
-        ver = w._version
         ent = self.entries.get(key)
-        if ent is not None and ent[0]() is base and ent[1] == ver and ent[3] == w.data_ptr():
-            return ent[2]
+        if ent is not None and ent.current(base, w):
+            return ent.buf
         lib = L.lib()
         n = lib.rgan_conv_pack_floats(ctypes.byref(d), which)
         if n == 0:
             return None  # the op reads the torch layout directly (or is unsupported: workspace says)
-        reuse = ent is not None and ent[0]() is base and ent[2].numel() == n
-        buf = ent[2] if reuse else torch.empty(n, dtype=torch.float32, device=w.device)
+        reuse = ent is not None and ent.ref() is base and ent.buf.numel() == n
+        buf = ent.buf if reuse else torch.empty(n, dtype=torch.float32, device=w.device)
         L.check(lib.rgan_conv_pack(ctypes.byref(d), which, L.ptr(w), L.ptr(buf), L.stream()), "rgan_conv_pack")
         # (the descriptor, layout and w's view geometry on its base let refresh() and the
         # optimizer's layout writer find the weight again: a view such as arch 1's dense layers
         # viewed as convolutions is a new tensor object at every call, so a weak reference to it
         # would die with the call and its layout would be repacked at every use)
         geo = None if w is base else (tuple(w.shape), tuple(w.stride()), w.storage_offset())
-        self.entries[key] = (weakref.ref(base, self._drop(key)), ver, buf, w.data_ptr(), d, which, geo)
+        self._put(key, base, w, buf, d, which, geo)
         return buf
 
     @staticmethod
@@ -119,19 +170,14 @@ class _PackCache:
         """The packed weight of an entry (its base parameter, or the view of it that was packed),
         or None when the entry is stale: the base is gone, or its storage no longer covers the
         saved view (e.g. ``p.data = smaller``) -- such an entry is never a valid layout source."""
-        base = ent[0]()
-        if base is None or ent[6] is None:
+        base = ent.ref()
+        if base is None or ent.geo is None:
             return base
-        shape, stride, offset = ent[6]
+        shape, stride, offset = ent.geo
         extent = offset + 1 + sum((n - 1) * st for n, st in zip(shape, stride))  # elements, all n >= 1
         if any(n == 0 for n in shape) or base.untyped_storage().nbytes() < extent * base.element_size():
             return None
         return base.as_strided(shape, stride, offset)
-
-    def _stale(self, key, ent):
-        """Drop an entry whose weight view can no longer be rebuilt (see _weight)."""
-        if ent[0]() is not None and self.entries.get(key) is ent:
-            del self.entries[key]
 
     def _snapshot(self):
         """list(entries.items()).  Building the list allocates, an allocation can start a garbage
@@ -143,102 +189,75 @@ class _PackCache:
             except RuntimeError:
                 continue
 
+    def _live(self, params):
+        """[(param index, key, entry, packed weight)] of the entries whose base is one of
+        ``params``.  On the way, every entry whose weight view can no longer be rebuilt (see
+        _weight) is dropped."""
+        idx = {id(p): i for i, p in enumerate(params)}
+        out = []
+        for key, ent in self._snapshot():
+            base, w = ent.ref(), self._weight(ent)
+            if base is not None and w is None:
+                if self.entries.get(key) is ent:
+                    del self.entries[key]
+            elif base is not None and id(base) in idx:
+                out.append((idx[id(base)], key, ent, w))
+        return out
+
     def refresh(self, params):
         """Repack, in one batched launch, every cached layout of ``params`` whose weight
         moved (called right after an optimizer step): the next convolutions find them
         current instead of packing one launch at a time."""
-        ids = {id(p) for p in params}
-        todo = []
-        for key, ent in self._snapshot():
-            base, w = ent[0](), self._weight(ent)
-            if base is not None and w is None:
-                self._stale(key, ent)
-                continue
-            if base is None or id(base) not in ids:
-                continue
-            if ent[1] == w._version and ent[3] == w.data_ptr():
-                continue
-            todo.append((key, ent, w))
+        todo = [(ent, w) for _, _, ent, w in self._live(params) if not ent.matches(w)]
         if not todo:
             return
         n = len(todo)
-        descs = (ctypes.POINTER(L.RganConv) * n)(*[ctypes.pointer(e[4]) for _, e, _ in todo])
-        which = (ctypes.c_int * n)(*[e[5] for _, e, _ in todo])
-        ws = (ctypes.c_void_p * n)(*[w.data_ptr() for _, _, w in todo])
-        outs = (ctypes.c_void_p * n)(*[e[2].data_ptr() for _, e, _ in todo])
+        descs = (ctypes.POINTER(L.RganConv) * n)(*[ctypes.pointer(e.d) for e, _ in todo])
+        which = (ctypes.c_int * n)(*[e.which for e, _ in todo])
+        ws = (ctypes.c_void_p * n)(*[w.data_ptr() for _, w in todo])
+        outs = (ctypes.c_void_p * n)(*[e.buf.data_ptr() for e, _ in todo])
         L.check(L.lib().rgan_conv_pack_batch(n, ctypes.cast(descs, ctypes.c_void_p), ctypes.cast(which, ctypes.c_void_p),
                                              ctypes.cast(ws, ctypes.c_void_p), ctypes.cast(outs, ctypes.c_void_p),
                                              L.stream()), "rgan_conv_pack_batch")
-        for key, ent, w in todo:
-            self.entries[key] = (ent[0], w._version, ent[2], w.data_ptr()) + ent[4:]
+        for ent, w in todo:
+            ent.mark(w)
 
     def layouts_of(self, params):
         """[(param index, key, entry)] of every cached layout of ``params`` (for
         rgan_adam_packed, which rewrites them with the new values)."""
-        idx = {id(p): i for i, p in enumerate(params)}
-        out = []
-        for key, ent in self._snapshot():
-            base, w = ent[0](), self._weight(ent)
-            if base is not None and w is None:
-                self._stale(key, ent)
-                continue
-            if base is None or id(base) not in idx or w.data_ptr() != params[idx[id(base)]].data_ptr():
-                continue
-            if w.numel() != params[idx[id(base)]].numel():
-                continue
-            out.append((idx[id(base)], key, ent))
-        return out
+        return [(i, key, ent) for i, key, ent, w in self._live(params)
+                if w.data_ptr() == params[i].data_ptr() and w.numel() == params[i].numel()]
 
     def mark_current(self, layouts):
         """The listed layouts were rewritten from their weights' current values."""
         for _, key, ent in layouts:
             w = self._weight(ent)
             if w is not None and self.entries.get(key) is ent:
-                self.entries[key] = (ent[0], w._version, ent[2], w.data_ptr()) + ent[4:]
-
-    def _drop(self, key):
-        def cb(_ref):
-            ent = self.entries.get(key)
-            if ent is not None and ent[0] is _ref:
-                del self.entries[key]
-        return cb
-
-    def clear(self):
-        self.entries.clear()
+                ent.mark(w)
 
 
 PACKS = _PackCache()
 
 
-class _FoldCache:
+class _FoldCache(_WeightCache):
     """Folded --NN_conv weights (Wt = A W A^T), one per (weight, version): like the packs,
     refolded only after an optimizer step.  A new Wt tensor is made per version so the
     pack cache (keyed by the Wt object) never sees a stale layout.  ``fn`` is the fold
     (nn_fold here; the image-layer patch weights use their own instance)."""
 
     def __init__(self, fn=None):
-        self.entries = {}
+        super().__init__()
         self.fn = fn
 
     def get(self, w, *args):
         base = w._base if w._base is not None else w
         key = (id(base),) + args
         ent = self.entries.get(key)
-        if ent is not None and ent[0]() is base and ent[1] == w._version and ent[2] == w.data_ptr():
-            return ent[3]
+        if ent is not None and ent.current(base, w):
+            return ent.buf
         wt = (self.fn or nn_fold)(w, *args)
-        self.entries[key] = (weakref.ref(base, self._drop(key)), w._version, w.data_ptr(), wt)
+        self._put(key, base, w, wt)
         return wt
-
-    def _drop(self, key):
-        def cb(_ref):
-            ent = self.entries.get(key)
-            if ent is not None and ent[0] is _ref:
-                del self.entries[key]
-        return cb
-
-    def clear(self):
-        self.entries.clear()
 
 
 FOLDS = _FoldCache()
@@ -313,6 +332,20 @@ def nn_unfold_grad(dwt, w_shape):
     return dw
 
 
+_UNSUPPORTED = ("unsupported conv {} for input {}", "unsupported conv dgrad {} for {}",
+                "unsupported conv wgrad {} for {}")  # per op 0 / 1 / 2 (rgan_conv_workspace's `which`)
+
+
+def _conv_prologue(d, which, w, geom, cache, x_shape, device):
+    """(cached pack of ``w`` or None, workspace) of op ``which`` on the descriptor ``d``; an op
+    the library has no kernel for answers 0 bytes and raises."""
+    packed = PACKS.get(w, which, geom, d) if cache else None
+    nbytes = L.lib().rgan_conv_workspace(ctypes.byref(d), which, int(packed is not None))
+    if nbytes == 0:
+        raise L.RganError(_UNSUPPORTED[which].format(geom, tuple(x_shape)))
+    return packed, L.workspace(nbytes, device)
+
+
 def conv_fwd(x, w, geom, bias=None, act="none", alpha=0.0, wscale=None, out=None, nchw_out=False, cache=False,
              post=None):
     """y = act(conv(x, w)*wscale + bias); x [B,Cin,H,W] any strides; w torch layout.
@@ -334,18 +367,13 @@ def conv_fwd(x, w, geom, bias=None, act="none", alpha=0.0, wscale=None, out=None
         out = (torch.empty((B, cout, Ho, Wo), dtype=torch.float32, device=x.device) if nchw_out
                else empty_nhwc(B, cout, Ho, Wo, x.device))
     d = _desc(x.shape, x.stride(), out.shape, out.stride(), geom)
-    lib = L.lib()
-    packed = PACKS.get(w, 0, geom, d) if cache else None
-    nbytes = lib.rgan_conv_workspace(ctypes.byref(d), 0, int(packed is not None))
-    if nbytes == 0:
-        raise L.RganError(f"unsupported conv {geom} for input {tuple(x.shape)}")
-    ws = L.workspace(nbytes, x.device)
+    packed, ws = _conv_prologue(d, 0, w, geom, cache, x.shape, x.device)
     if post is not None:
         post.fused = False
         if bias is None and act == "none" and _conv_post(0, d, x, w, packed, wscale, out, ws, post) is not False:
             return out
-    L.check(lib.rgan_conv_fwd(ctypes.byref(d), L.ptr(x), L.ptr(w), L.ptr(packed), L.ptr(wscale), L.ptr(bias),
-                              L.ptr(out), L.ACT[act], float(alpha), L.ptr(ws), ws.numel(), L.stream()),
+    L.check(L.lib().rgan_conv_fwd(ctypes.byref(d), L.ptr(x), L.ptr(w), L.ptr(packed), L.ptr(wscale), L.ptr(bias),
+                                  L.ptr(out), L.ACT[act], float(alpha), L.ptr(ws), ws.numel(), L.stream()),
             "rgan_conv_fwd")
     return out
 
@@ -370,11 +398,7 @@ def conv_fwd_bn(x, w, geom, bias=None, wscale=None, cache=False, segs=1):
     S = lib.rgan_conv_bn_segments(ctypes.byref(d), int(segs))
     if S <= 0:
         return conv_fwd(x, w, geom, bias=bias, wscale=wscale, out=out, cache=cache), None, 0
-    packed = PACKS.get(w, 0, geom, d) if cache else None
-    nbytes = lib.rgan_conv_workspace(ctypes.byref(d), 0, int(packed is not None))
-    if nbytes == 0:
-        raise L.RganError(f"unsupported conv {geom} for input {tuple(x.shape)}")
-    ws = L.workspace(nbytes, x.device)
+    packed, ws = _conv_prologue(d, 0, w, geom, cache, x.shape, x.device)
     part = torch.empty((S, 2, cout), dtype=torch.float64, device=x.device)
     fused = L.c_int(0)
     L.check(lib.rgan_conv_fwd_bn(ctypes.byref(d), L.ptr(x), L.ptr(w), L.ptr(packed), L.ptr(wscale), L.ptr(bias),
@@ -460,18 +484,13 @@ def conv_dgrad(dy, w, geom, x_shape, wscale=None, out=None, like=None, cache=Fal
         else:
             out = empty_nhwc(B, cin, H, W, dy.device)
     d = _desc(out.shape, out.stride(), dy.shape, dy.stride(), geom)
-    lib = L.lib()
-    packed = PACKS.get(w, 1, geom, d) if cache else None
-    nbytes = lib.rgan_conv_workspace(ctypes.byref(d), 1, int(packed is not None))
-    if nbytes == 0:
-        raise L.RganError(f"unsupported conv dgrad {geom} for {tuple(x_shape)}")
-    ws = L.workspace(nbytes, dy.device)
+    packed, ws = _conv_prologue(d, 1, w, geom, cache, x_shape, dy.device)
     if post is not None:
         post.fused = False
         if _conv_post(1, d, dy, w, packed, wscale, out, ws, post) is not False:
             return out
-    L.check(lib.rgan_conv_dgrad(ctypes.byref(d), L.ptr(dy), L.ptr(w), L.ptr(packed), L.ptr(wscale), L.ptr(out),
-                                L.ptr(ws), ws.numel(), L.stream()), "rgan_conv_dgrad")
+    L.check(L.lib().rgan_conv_dgrad(ctypes.byref(d), L.ptr(dy), L.ptr(w), L.ptr(packed), L.ptr(wscale), L.ptr(out),
+                                    L.ptr(ws), ws.numel(), L.stream()), "rgan_conv_dgrad")
     return out
 
 
@@ -503,8 +522,7 @@ def g1_fwd_bn(x, w, gamma, beta, eps, momentum, running_mean, running_var, num_b
 def g1_wgrad(x, dy, w_shape, out=None, into=None):
     """dW of G's first layer (rgan_g1_wgrad); ``out``: add into it, ``into``: write into it."""
     L.require_cuda(x, dy)
-    if not is_nhwc(dy):
-        dy = dy.contiguous(memory_format=torch.channels_last)
+    dy = as_nhwc(dy)
     dw = out if out is not None else (into if into is not None else
                                       torch.empty(w_shape, dtype=torch.float32, device=x.device))
     L.check(L.lib().rgan_g1_wgrad(L.ptr(x), x.shape[0], x.shape[1], L.ptr(dy), w_shape[1], L.ptr(dw),
@@ -541,16 +559,11 @@ def conv_wgrad(x, dy, geom, w_shape, with_bias=False, out=None, out_bias=None, i
         if acc != (out_bias is not None):
             raise L.RganError("conv_wgrad: accumulate weight and bias gradients together")
         db = out_bias if acc else torch.empty(dy.shape[1], dtype=torch.float32, device=x.device)
-        if not is_nhwc(dy):
-            dy = dy.contiguous(memory_format=torch.channels_last)
+        dy = as_nhwc(dy)
     d = _desc(x.shape, x.stride(), dy.shape, dy.stride(), geom)
-    lib = L.lib()
-    nbytes = lib.rgan_conv_workspace(ctypes.byref(d), 2, 0)
-    if nbytes == 0:
-        raise L.RganError(f"unsupported conv wgrad {geom} for {tuple(x.shape)}")
-    ws = L.workspace(nbytes, x.device)
-    L.check(lib.rgan_conv_wgrad_rows(ctypes.byref(d), L.ptr(x), L.ptr(dy), L.ptr(dw), L.ptr(db), int(bias_row0),
-                                     int(acc), L.ptr(ws), ws.numel(), L.stream()), "rgan_conv_wgrad_rows")
+    _, ws = _conv_prologue(d, 2, None, geom, False, x.shape, x.device)
+    L.check(L.lib().rgan_conv_wgrad_rows(ctypes.byref(d), L.ptr(x), L.ptr(dy), L.ptr(dw), L.ptr(db), int(bias_row0),
+                                         int(acc), L.ptr(ws), ws.numel(), L.stream()), "rgan_conv_wgrad_rows")
     return dw, db
 
 
@@ -596,8 +609,7 @@ def bn_finalize(moments, nranks, C, eps, momentum, running_mean=None, running_va
 
 
 def bn_backward_sums(da, y, stats, gamma, beta, act="none", alpha=0.0):
-    if not is_nhwc(da):
-        da = da.contiguous(memory_format=torch.channels_last)
+    da = as_nhwc(da)
     P, C, sp, sc = _pc(y)
     _, _, dsp, dsc = _pc(da)
     sums = torch.empty(2 * C, dtype=torch.float64, device=y.device)
@@ -615,8 +627,7 @@ def bn_backward_apply(da, y, stats, gamma, beta, act, alpha, sums, P_global, nee
     dy = torch.empty_like(y) if out is None else out
     if dy.stride() != y.stride():
         raise L.RganError("bn_backward_apply: out must have y's strides")
-    dgamma = torch.empty(C, dtype=torch.float32, device=y.device) if need_affine and gamma is not None else None
-    dbeta = torch.empty(C, dtype=torch.float32, device=y.device) if need_affine and beta is not None else None
+    dgamma, dbeta = affine_grad_bufs(y, gamma, beta, need_affine, need_affine)
     L.check(L.lib().rgan_bn_backward_apply(L.ptr(da), dsp, dsc, L.ptr(y), P, C, sp, sc, L.ptr(stats),
                                            L.ptr(gamma), L.ptr(beta), L.ACT[act], float(alpha), L.ptr(sums),
                                            int(P_global), L.ptr(dy), sp, sc, L.ptr(dgamma), L.ptr(dbeta),
@@ -630,8 +641,7 @@ def bn_backward_sums_apply(da, y, stats, gamma, beta, act, alpha, add=None, out=
     one launch for <= 2048 rows, C % 16 == 0 and C >= 1024): sums as bn_backward_sums returns
     them, dy = BN-backward(da * act') + add; dgamma / dbeta (given buffers) written or, with
     accumulate_affine, added into.  Dense NHWC da / y / out / add; add may be out itself."""
-    if not is_nhwc(da):
-        da = da.contiguous(memory_format=torch.channels_last)
+    da = as_nhwc(da)
     P, C, _, _ = _pc(y)
     dy = torch.empty_like(y) if out is None else out
     if not is_nhwc(dy) or (add is not None and not is_nhwc(add)):
@@ -691,8 +701,7 @@ def bn_backward_segments(da, y, stats, gamma, beta, act, alpha, need_gamma, need
     (dense NHWC da, y, out); dgamma / dbeta summed over the segments."""
     P, C, _, _ = _pc(y)
     nseg = stats.shape[0]
-    dgamma = torch.empty(C, dtype=torch.float32, device=y.device) if need_gamma and gamma is not None else None
-    dbeta = torch.empty(C, dtype=torch.float32, device=y.device) if need_beta and beta is not None else None
+    dgamma, dbeta = affine_grad_bufs(y, gamma, beta, need_gamma, need_beta)
     lib = L.lib()
     ws = L.workspace(nseg * lib.rgan_bn_partial_bytes(P // nseg, C), y.device)
     L.check(lib.rgan_bn_backward_segments(L.ptr(da), L.ptr(y), P, C, nseg, L.ptr(stats), L.ptr(gamma), L.ptr(beta),
@@ -709,8 +718,7 @@ def bn_backward_parts(g, y, stats, gamma, beta, post, need_gamma, need_beta, out
     if stats.dim() == 1:
         stats = stats.view(1, -1)
     dy = torch.empty_like(y) if out is None else out
-    dgamma = torch.empty(C, dtype=torch.float32, device=y.device) if need_gamma and gamma is not None else None
-    dbeta = torch.empty(C, dtype=torch.float32, device=y.device) if need_beta and beta is not None else None
+    dgamma, dbeta = affine_grad_bufs(y, gamma, beta, need_gamma, need_beta)
     sums = torch.empty((nseg, 2, C), dtype=torch.float64, device=y.device)
     L.check(L.lib().rgan_bn_backward_parts(L.ptr(g), L.ptr(y), P, C, nseg, L.ptr(stats), L.ptr(gamma), L.ptr(beta),
                                            L.ptr(post.part), int(post.S), int(post.phases), L.ptr(dy),
@@ -730,15 +738,13 @@ def bn_apply(y, stats, gamma, beta, act="none", alpha=0.0, out=None):
 
 
 def bn_backward(da, y, stats, gamma, beta, act="none", alpha=0.0, need_affine=True, out=None):
-    if not is_nhwc(da):
-        da = da.contiguous(memory_format=torch.channels_last)
+    da = as_nhwc(da)
     P, C, sp, sc = _pc(y)
     _, _, dsp, dsc = _pc(da)
     dy = torch.empty_like(y) if out is None else out
     if dy.stride() != y.stride():
         raise L.RganError("bn_backward: out must have y's strides")
-    dgamma = torch.empty(C, dtype=torch.float32, device=y.device) if need_affine and gamma is not None else None
-    dbeta = torch.empty(C, dtype=torch.float32, device=y.device) if need_affine and beta is not None else None
+    dgamma, dbeta = affine_grad_bufs(y, gamma, beta, need_affine, need_affine)
     lib = L.lib()
     part = L.workspace(lib.rgan_bn_partial_bytes(P, C), y.device)
     L.check(lib.rgan_bn_backward(L.ptr(da), dsp, dsc, L.ptr(y), P, C, sp, sc, L.ptr(stats), L.ptr(gamma),
@@ -751,8 +757,7 @@ def bn_backward_apply_ex(da, y, stats, gamma, beta, act, alpha, sums, P_global, 
                          dgamma=None, dbeta=None, accumulate_affine=False):
     """dy = BN-backward(da * act') + add; dgamma/dbeta (given buffers) written or, with
     accumulate_affine, added into."""
-    if not is_nhwc(da):
-        da = da.contiguous(memory_format=torch.channels_last)
+    da = as_nhwc(da)
     P, C, sp, sc = _pc(y)
     _, _, dsp, dsc = _pc(da)
     dy = torch.empty_like(y) if out is None else out
@@ -1098,17 +1103,18 @@ class DeviceRNG:
 
 
 # ------------------------------------------------------------------ Adam / data
+def _arrays(params, *others):
+    """void*[n] of ``params``' and each other tensor list's addresses, then long long[n] of
+    ``params``' element counts: each array as the void* the C ABI takes."""
+    n = max(len(params), 1)
+    arrs = [(ctypes.c_void_p * n)(*[t.data_ptr() for t in ts]) for ts in (params,) + others]
+    arrs.append((ctypes.c_longlong * n)(*[p.numel() for p in params]))
+    return [ctypes.cast(a, ctypes.c_void_p) for a in arrs]
+
+
 def adam(params, grads, exp_avgs, exp_avg_sqs, hyper, step):
-    n = len(params)
-    arr = ctypes.c_void_p * max(n, 1)
-    P = arr(*[p.data_ptr() for p in params])
-    G = arr(*[g.data_ptr() for g in grads])
-    M = arr(*[m.data_ptr() for m in exp_avgs])
-    V = arr(*[v.data_ptr() for v in exp_avg_sqs])
-    N = (ctypes.c_longlong * max(n, 1))(*[p.numel() for p in params])
-    L.check(L.lib().rgan_adam(n, ctypes.cast(P, ctypes.c_void_p), ctypes.cast(G, ctypes.c_void_p),
-                              ctypes.cast(M, ctypes.c_void_p), ctypes.cast(V, ctypes.c_void_p),
-                              ctypes.cast(N, ctypes.c_void_p), L.ptr(hyper), L.ptr(step), L.stream()), "rgan_adam")
+    P, G, M, V, N = _arrays(params, grads, exp_avgs, exp_avg_sqs)
+    L.check(L.lib().rgan_adam(len(params), P, G, M, V, N, L.ptr(hyper), L.ptr(step), L.stream()), "rgan_adam")
 
 
 def adam_packed(params, grads, exp_avgs, exp_avg_sqs, hyper, step, layouts):
@@ -1117,20 +1123,12 @@ def adam_packed(params, grads, exp_avgs, exp_avg_sqs, hyper, step, layouts):
     ``step``: the count, a view whose next float is the group's arrival ticket (optim.Adam)."""
     if step.untyped_storage().nbytes() < 4 * (step.storage_offset() + 2):
         raise L.RganError("adam_packed: step must be followed by its arrival-ticket word (float[2] storage)")
-    n = len(params)
-    arr = ctypes.c_void_p * max(n, 1)
-    P = arr(*[p.data_ptr() for p in params])
-    G = arr(*[g.data_ptr() for g in grads])
-    M = arr(*[m.data_ptr() for m in exp_avgs])
-    V = arr(*[v.data_ptr() for v in exp_avg_sqs])
-    N = (ctypes.c_longlong * max(n, 1))(*[p.numel() for p in params])
+    P, G, M, V, N = _arrays(params, grads, exp_avgs, exp_avg_sqs)
     k = len(layouts)
     packs = (L.RganAdamPack * max(k, 1))()
     for i, (j, _key, ent) in enumerate(layouts):
-        packs[i] = L.RganAdamPack(j, ent[5], ctypes.pointer(ent[4]), ent[2].data_ptr())
-    L.check(L.lib().rgan_adam_packed(n, ctypes.cast(P, ctypes.c_void_p), ctypes.cast(G, ctypes.c_void_p),
-                                     ctypes.cast(M, ctypes.c_void_p), ctypes.cast(V, ctypes.c_void_p),
-                                     ctypes.cast(N, ctypes.c_void_p), L.ptr(hyper), L.ptr(step), k,
+        packs[i] = L.RganAdamPack(j, ent.which, ctypes.pointer(ent.d), ent.buf.data_ptr())
+    L.check(L.lib().rgan_adam_packed(len(params), P, G, M, V, N, L.ptr(hyper), L.ptr(step), k,
                                      ctypes.cast(packs, ctypes.c_void_p), L.stream()), "rgan_adam_packed")
 
 
@@ -1328,14 +1326,8 @@ def ema_update(avgs, params, hyper, count):
                               f"{tuple(p.shape)} / {p.stride()}")
         if p.numel() and 1 + sum((s - 1) * st for s, st in zip(p.shape, p.stride())) != p.numel():
             raise L.RganError("ema_update: tensors must be dense (the kernel walks numel floats of storage)")
-    n = len(params)
-    arr = ctypes.c_void_p * max(n, 1)
-    A = arr(*[a.data_ptr() for a in avgs])
-    P = arr(*[p.data_ptr() for p in params])
-    N = (ctypes.c_longlong * max(n, 1))(*[p.numel() for p in params])
-    L.check(L.lib().rgan_ema_update(n, ctypes.cast(A, ctypes.c_void_p), ctypes.cast(P, ctypes.c_void_p),
-                                    ctypes.cast(N, ctypes.c_void_p), L.ptr(hyper), L.ptr(count), L.stream()),
-            "rgan_ema_update")
+    P, A, N = _arrays(params, avgs)
+    L.check(L.lib().rgan_ema_update(len(params), A, P, N, L.ptr(hyper), L.ptr(count), L.stream()), "rgan_ema_update")
 
 
 # ------------------------------------------------------------------ GEMM arithmetic

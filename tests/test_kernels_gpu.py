@@ -957,13 +957,13 @@ def test_pack_batch_refresh(K):
     ids = {id(p) for p in params}
     checked = 0
     for ent in list(K.PACKS.entries.values()):
-        base, w = ent[0](), K.PACKS._weight(ent)
+        base, w = ent.ref(), K.PACKS._weight(ent)
         if base is None or id(base) not in ids:
             continue
-        assert ent[1] == w._version
-        fresh = torch.empty_like(ent[2])
-        L.check(L.lib().rgan_conv_pack(ctypes.byref(ent[4]), ent[5], L.ptr(w), L.ptr(fresh), L.stream()), "pack")
-        assert torch.equal(fresh, ent[2])
+        assert ent.ver == w._version
+        fresh = torch.empty_like(ent.buf)
+        L.check(L.lib().rgan_conv_pack(ctypes.byref(ent.d), ent.which, L.ptr(w), L.ptr(fresh), L.stream()), "pack")
+        assert torch.equal(fresh, ent.buf)
         checked += 1
     assert checked >= 17
 
@@ -983,7 +983,7 @@ def test_pack_cache_keeps_views_current(K):
     p.grad = torch.randn_like(p)
     Adam([p], lr=1e-3, betas=(0.5, 0.999)).step()
     ent = K.PACKS.layouts_of([p])[0][2]
-    assert ent[1] == p._version  # rewritten from the stepped values: current
+    assert ent.ver == p._version  # rewritten from the stepped values: current
     y1 = K.conv_fwd(x, p.view(1, 512, 4, 4), g, cache=True)
     with torch.backends.cudnn.flags(enabled=False):
         ref = F.conv2d(x.double(), p.detach().double().view(1, 512, 4, 4))
@@ -1057,11 +1057,11 @@ def test_adam_writes_packed_layouts(K):
         assert len(lay) == before
         for _, _, ent in lay:
             w = K.PACKS._weight(ent)
-            assert ent[1] == w._version  # current: the next conv reuses it
-            fresh = torch.empty_like(ent[2])
-            L.check(L.lib().rgan_conv_pack(ctypes.byref(ent[4]), ent[5], L.ptr(w), L.ptr(fresh), L.stream()), "pack")
+            assert ent.ver == w._version  # current: the next conv reuses it
+            fresh = torch.empty_like(ent.buf)
+            L.check(L.lib().rgan_conv_pack(ctypes.byref(ent.d), ent.which, L.ptr(w), L.ptr(fresh), L.stream()), "pack")
             torch.cuda.synchronize()
-            assert torch.equal(fresh, ent[2]), (tuple(w.shape), ent[5])
+            assert torch.equal(fresh, ent.buf), (tuple(w.shape), ent.which)
 
 
 def test_device_rng(K):

@@ -32,8 +32,8 @@ def main():
         base = w._base if w._base is not None else w
         key = (id(base), which, geom, d.cin, d.cout, d.hin, d.win, d.hout, d.wout)
         ent = K.PACKS.entries.get(key)
-        hit = ent is not None and ent[0]() is base and ent[1] == w._version and ent[3] == w.data_ptr()
-        why = "hit" if hit else ("new" if ent is None else ("version" if ent[1] != w._version else "other"))
+        hit = ent is not None and ent.current(base, w)
+        why = "hit" if hit else ("new" if ent is None else ("version" if ent.ver != w._version else "other"))
         log.append((tuple(w.shape), "view" if w._base is not None else "param", which, why))
         return orig_get(w, which, geom, d)
     K.PACKS.get = get
