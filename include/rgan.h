@@ -30,7 +30,8 @@ extern "C" {
  * 3: adds rgan_conv_wgrad_rows.  4: adds rgan_bn_segment_apply and rgan_bn_backward_sums_apply.
  * rgan_diffaug_workspace, rgan_diffaug, rgan_ema_update, rgan_diffaug_p, rgan_ada_update,
  * rgan_ada_adjust, rgan_lecam, rgan_lecam_finish, rgan_diffaug_geo_workspace and rgan_diffaug_geo
- * are additive within revision 4 (nothing else changed). */
+ * are additive within revision 4 (nothing else changed), and so are rgan_sort_segments with its
+ * _tile and _ws_bytes and the rgan_swd_ entry points. */
 #define RGAN_ABI_VERSION 4
 
 /* Activation codes fused into epilogues (GLI:345,370,388,417,437,450; SELU GLI:338). */
@@ -679,6 +680,87 @@ int rgan_rng_fill(float* out, long long n, int kind, unsigned long long seed, un
                   void* stream);
 int rgan_rng_choice(long long* out, int N, int n, unsigned long long seed, unsigned long long* counter,
                     void* stream);
+
+/* ---- segmented key sort (csrc/sort.hip; the sliced Wasserstein metric's; no reference counterpart) ----
+ * (additive within ABI revision 4: no existing entry point changed)
+ * rgan_sort_segments: nseg contiguous segments of len fp32 keys each, in[s len .. (s + 1) len), each
+ * sorted ascending into out; keys only.  Order: the total order of the bit patterns, key(u) =
+ * u ^ (u >> 31 ? 0xffffffff : 0x80000000) compared unsigned, so -0 < +0 and NaN patterns sort by
+ * their bits (negative ones first, positive ones last); out holds the input's own bit patterns.
+ * A least-significant-digit radix sort of 4 passes x 8 bits over tiles of rgan_sort_segments_tile()
+ * keys (one block each): per pass a histogram per tile, one exclusive scan over (digit, tile) per
+ * segment, and a stable scatter whose ranks come from wave ballots and scans, never from the order
+ * in which atomics arrive: equal inputs give equal bits, run after run.  The passes go in -> tmp ->
+ * out -> tmp -> out: tmp holds nseg len floats and is scratch; out may be in (in is read by the
+ * first pass only), tmp may be neither.  in, out, tmp need 4-byte alignment only.  ws: at least
+ * rgan_sort_segments_ws_bytes(nseg, len) bytes (256 uint32 per tile), 4-byte aligned.
+ * Limits: nseg >= 1, len >= 1, nseg len < 2^31.  Anything else, a null pointer, tmp == in or out, or
+ * a short ws is refused (RGAN_EINVAL) without a launch; the ws_bytes function answers 0 then. */
+int rgan_sort_segments_tile(void);
+size_t rgan_sort_segments_ws_bytes(int nseg, int len);
+int rgan_sort_segments(const float* in, float* out, float* tmp, int nseg, int len, void* ws,
+                       size_t ws_bytes, void* stream);
+
+/* ---- sliced Wasserstein distance over Laplacian-pyramid patches (csrc/swd.hip; --rgan_swd_every,
+ * python -m relativisticgan_amd.evaluate; Karras et al., ICLR 2018, section 5; the reference's
+ * quality metric is FID, code/fid.py, which needs a downloaded network) ----
+ * (additive within ABI revision 4: no existing entry point changed)
+ * Images are planar fp32 [N][C][S][S] with values 0..255, 1 <= C <= 4.  Every entry point refuses
+ * (RGAN_EINVAL, nothing launched) a null pointer, a size <= 0 and what its own lines add.
+ *
+ * rgan_swd_load_u8: out[n][c][y][x] = in[n s0 + c s1 + y s2 + x s3], strides = host long long[4] in
+ * elements, each >= 0 (CHW datasets and the HWC output of rgan_images_to_u8 alike).
+ *
+ * rgan_swd_pyr_down: out [N][C][S/2][S/2] = the even rows and columns of in filtered with the 5x5
+ * binomial [1 4 6 4 1]/16 x [1 4 6 4 1]/16, the border mirrored without repeating the edge
+ * (-1 -> 1, -2 -> 2, S -> S - 2, S + 1 -> S - 3).  S a power of two >= 32; out must not be in.
+ * rgan_swd_laplace: out = fine - up(coarse), fine and out [N][C][S][S], coarse [N][C][S/2][S/2]:
+ * up puts coarse on the even positions of a zero image of side S, applies the same filter with the
+ * same mirror rule to that image and multiplies by 4; the zero image is never formed.  out may be
+ * fine (a thread reads only its own element of fine); it must not be coarse.  S as for pyr_down.
+ * Both add their taps in double, rows then columns ascending, and round once to fp32.
+ *
+ * rgan_swd_positions: pos[i] = 3 + floor(u[i] (side - 6)) for i < n, u in [0, 1) as rgan_rng_fill
+ * kind 1 draws it (a multiple of 2^-24: the product is formed exactly in integers; u outside
+ * [0, 1) is clamped), so 3 <= pos <= side - 4.  side >= 7.
+ *
+ * rgan_swd_descriptors: for image n < N and patch p < P with centre (y, x) = pos[(n P + p) 2 + {0, 1}]
+ * (int32; clamped to [3, S - 4], so no read leaves the image), row m = n P + p of desc [N P][K],
+ * K = 49 C: desc[m][49 c + 7 dy + dx] = img[n][c][y + dy - 3][x + dx - 3], and part[n][c] = double
+ * {sum, sum of squares} of the row values of channel c (part: N C 2 doubles).  S >= 7,
+ * N P < 2^31.  One block per image; the sums are added in a fixed order.
+ * rgan_swd_normalize: over M rows of desc and the nparts images' part (M 49 values per channel):
+ * stats[c] = double {mean, population standard deviation} (stats: C 2 doubles), then in place
+ * desc = (float)(((double)desc - mean) / std), each element rounded once.  A channel whose std is 0
+ * becomes zeros.  The sums are finished by one block in a fixed order: equal inputs, equal bits.
+ * rgan_swd_stats_ws_bytes(nparts, C): bytes of part followed by stats (0 for bad sizes).
+ *
+ * rgan_swd_unit_columns: dirs [K][D] in place, column d divided by its L2 norm (sum of squares in
+ * double over ascending k, one rounding per element); a zero column stays.  K <= 196, D <= 512.
+ * rgan_swd_project: proj[d][m] = sum_k desc[m][k] dirs[k][d], proj [D][M] (a direction's values
+ * contiguous: the segments rgan_sort_segments takes).  fp32, one fused multiply-add per k in
+ * ascending k from 0, through LDS tiles of 64 rows x 64 directions x 49 k.  M D < 2^31, K <= 196,
+ * D <= 512.
+ *
+ * rgan_swd_l1: out[0] = sum_i |a[i] - b[i]| over n < 2^31 floats, in double: per-thread strided sums,
+ * a block's threads, then the blocks, all in an order fixed by n.  ws: rgan_swd_l1_ws_bytes(n). */
+int rgan_swd_load_u8(const uint8_t* in, int N, int C, int S, const long long* strides, float* out,
+                     void* stream);
+int rgan_swd_pyr_down(const float* in, int N, int C, int S, float* out, void* stream);
+int rgan_swd_laplace(const float* fine, const float* coarse, int N, int C, int S, float* out,
+                     void* stream);
+int rgan_swd_positions(const float* u, long long n, int side, int* pos, void* stream);
+size_t rgan_swd_stats_ws_bytes(int nparts, int C);
+int rgan_swd_descriptors(const float* img, int N, int C, int S, int P, const int* pos, float* desc,
+                         double* part, void* stream);
+int rgan_swd_normalize(float* desc, long long M, int C, const double* part, int nparts,
+                       double* stats, void* stream);
+int rgan_swd_unit_columns(float* dirs, int K, int D, void* stream);
+int rgan_swd_project(const float* desc, const float* dirs, int M, int K, int D, float* proj,
+                     void* stream);
+size_t rgan_swd_l1_ws_bytes(long long n);
+int rgan_swd_l1(const float* a, const float* b, long long n, double* out, void* ws, size_t ws_bytes,
+                void* stream);
 
 #ifdef __cplusplus
 }

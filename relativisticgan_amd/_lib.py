@@ -144,6 +144,20 @@ _SIGS = {
     "rgan_ada_adjust": (c_int, [c_vp, c_vp, c_vp]),
     "rgan_lecam": (c_int, [c_vp, c_vp, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_vp]),
     "rgan_lecam_finish": (c_int, [c_vp, c_int, c_int, c_vp, c_vp, c_vp, c_vp]),
+    "rgan_sort_segments_tile": (c_int, []),
+    "rgan_sort_segments_ws_bytes": (c_sz, [c_int, c_int]),
+    "rgan_sort_segments": (c_int, [c_vp, c_vp, c_vp, c_int, c_int, c_vp, c_sz, c_vp]),
+    "rgan_swd_load_u8": (c_int, [c_vp, c_int, c_int, c_int, c_vp, c_vp, c_vp]),
+    "rgan_swd_pyr_down": (c_int, [c_vp, c_int, c_int, c_int, c_vp, c_vp]),
+    "rgan_swd_laplace": (c_int, [c_vp, c_vp, c_int, c_int, c_int, c_vp, c_vp]),
+    "rgan_swd_positions": (c_int, [c_vp, c_ll, c_int, c_vp, c_vp]),
+    "rgan_swd_stats_ws_bytes": (c_sz, [c_int, c_int]),
+    "rgan_swd_descriptors": (c_int, [c_vp, c_int, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_vp]),
+    "rgan_swd_normalize": (c_int, [c_vp, c_ll, c_int, c_vp, c_int, c_vp, c_vp]),
+    "rgan_swd_unit_columns": (c_int, [c_vp, c_int, c_int, c_vp]),
+    "rgan_swd_project": (c_int, [c_vp, c_vp, c_int, c_int, c_int, c_vp, c_vp]),
+    "rgan_swd_l1_ws_bytes": (c_sz, [c_ll]),
+    "rgan_swd_l1": (c_int, [c_vp, c_vp, c_ll, c_vp, c_vp, c_sz, c_vp]),
     "rgan_set_gemm_emulation": (c_int, [c_int]),
     "rgan_profile_begin": (c_int, [c_int]),
     "rgan_profile_end": (c_int, [c_vp, c_vp, c_vp]),

@@ -17,7 +17,10 @@ after errD and the WGAN-GP penalty; lazily every K-th iteration with weight GAMM
 ``reg_weight``; 0 = off, the default; not with --rgan_pac 2), ``--rgan_lecam LAMBDA``
 with ``--rgan_lecam_beta`` / ``--rgan_lecam_start`` (LeCam regularisation: LAMBDA times the squared
 distance of D's outputs from moving averages of its outputs on the other kind of batch, added to
-the D step without another pass of D; 0 = off, the default; see ``validate_lecam``), ``--rgan_pac 2``
+the D step without another pass of D; 0 = off, the default; see ``validate_lecam``),
+``--rgan_swd_every K`` with ``--rgan_swd_images N`` (log the sliced Wasserstein distance between
+the training images and G's samples after every K-th iteration; 0 = off, the default;
+single-process runs only, see ``validate_swd``; relativisticgan_amd/swd.py), ``--rgan_pac 2``
 (the PacGAN-2 script, code/GAN_losses_iter_PAC.py, which shares this CLI) and
 ``--rgan_script`` (the defaults of GAN_losses_iter / GAN_losses_iter_art / GAN_losses_iter_PAC).
 """
@@ -130,6 +133,14 @@ def make_parser(script="GAN_losses_iter"):
     p.add_argument("--rgan_perf_log", type="bool", default=True,
                    help="after each reference log line, a line with img/s and MFMA%% of the training "
                         "iterations since the previous one (sample PNGs, checkpoints and extra images excluded)")
+    p.add_argument("--rgan_swd_every", type=int, default=0,
+                   help="after every K-th iteration, log the sliced Wasserstein distance (x 1000, per Laplacian-"
+                        "pyramid level and their average; Karras et al., ICLR 2018) between the training images and "
+                        "G's samples (the averaged generator's with --rgan_ema_G); single-process runs only "
+                        "(default 0: off)")
+    p.add_argument("--rgan_swd_images", type=int, default=8192,
+                   help="images per set for the sliced Wasserstein distance (--rgan_swd_every and "
+                        "python -m relativisticgan_amd.evaluate), at most the dataset's size (default 8192)")
     p.add_argument("--rgan_synthetic", type=int, default=0,
                    help="use N synthetic images instead of an image folder (no torchvision here)")
     return p
@@ -152,9 +163,30 @@ def parse(argv=None):
         validate_reg(ns.rgan_r1, ns.rgan_r2, ns.rgan_reg_every, ns.pac)
         validate_ada(ns.rgan_diffaug, ns.rgan_aug_p, ns.rgan_ada_target, ns.rgan_ada_interval, ns.rgan_ada_kimg)
         validate_lecam(ns.rgan_lecam, ns.rgan_lecam_beta, ns.rgan_lecam_start)
+        validate_swd(ns.rgan_swd_every, ns.rgan_swd_images, ns.image_size)
     except ValueError as e:
         parser.error(str(e))
     return ns
+
+
+def validate_swd(every, images=8192, image_size=64, world=None):
+    """Check --rgan_swd_every / --rgan_swd_images (ValueError otherwise); True when the metric is on.
+    Refused under data parallelism (WORLD_SIZE > 1): the metric runs G on one rank, and a SyncBN
+    forward there would wait for the others."""
+    import os
+    if every < 0:
+        raise ValueError(f"--rgan_swd_every must be >= 0 (0 = off), got {every}")
+    if images < 1:
+        raise ValueError(f"--rgan_swd_images must be >= 1, got {images}")
+    if every == 0:
+        return False
+    if image_size < 32 or image_size & (image_size - 1):
+        raise ValueError(f"--rgan_swd_every needs an --image_size that is a power of two >= 32, got {image_size}")
+    world = int(os.environ.get("WORLD_SIZE", "1")) if world is None else world
+    if world > 1:
+        raise ValueError("--rgan_swd_every is for single-process runs: under data parallelism evaluate a checkpoint "
+                         "with python -m relativisticgan_amd.evaluate instead")
+    return True
 
 
 ADA_DEFAULTS = (4, 500.0)  # --rgan_ada_interval, --rgan_ada_kimg

@@ -1360,3 +1360,159 @@ def profile_end():
             kern.append({"name": name.value.decode(), "ms": kms.value, "flops": kfl.value, "launches": kn.value,
                          "tflops": kfl.value / kms.value / 1e9 if kms.value > 0 else 0.0})
     return {"ms": ms.value, "flops": fl.value, "launches": n.value, "kernels": kern}
+
+
+# ------------------------------------------------------------------ segmented sort
+def _f32c(what, *ts):
+    for t in ts:
+        L.require_cuda(t)
+        if t.dtype != torch.float32 or not t.is_contiguous():
+            raise L.RganError(f"{what}: needs contiguous float32 device tensors")
+
+
+def sort_segments_tile():
+    """Keys per block of rgan_sort_segments (a segment takes ceil(len / tile) blocks)."""
+    return int(L.lib().rgan_sort_segments_tile())
+
+
+def sort_segments(x, out=None, tmp=None):
+    """Each row of ``x`` [nseg][len] sorted ascending in the total order of its bit patterns
+    (include/rgan.h rgan_sort_segments) into ``out`` (may be ``x``); ``tmp``: scratch of x's size."""
+    if x.dim() != 2 or x.numel() == 0 or x.numel() >= 2 ** 31:
+        raise L.RganError(f"sort_segments: needs [nseg][len] with 1 <= nseg len < 2^31, got {tuple(x.shape)}")
+    out = torch.empty_like(x) if out is None else out
+    tmp = torch.empty_like(x) if tmp is None else tmp
+    _f32c("sort_segments", x, out, tmp)
+    if out.numel() != x.numel() or tmp.numel() != x.numel() or tmp.data_ptr() in (x.data_ptr(), out.data_ptr()):
+        raise L.RganError("sort_segments: out and tmp must have x's size, and tmp must be neither of them")
+    nseg, n = x.shape
+    nbytes = L.lib().rgan_sort_segments_ws_bytes(nseg, n)
+    ws = L.workspace(nbytes, x.device)
+    L.check(L.lib().rgan_sort_segments(L.ptr(x), L.ptr(out), L.ptr(tmp), nseg, n, L.ptr(ws), nbytes, L.stream()),
+            "rgan_sort_segments")
+    return out
+
+
+# ------------------------------------------------------------------ sliced Wasserstein distance
+def _swd_images(what, x):
+    _f32c(what, x)
+    if x.dim() != 4 or x.shape[2] != x.shape[3] or not 1 <= x.shape[1] <= 4 or x.numel() == 0:
+        raise L.RganError(f"{what}: needs planar [N][C][S][S] images with C <= 4, got {tuple(x.shape)}")
+    return tuple(int(v) for v in x.shape[:3])
+
+
+def swd_load_u8(x, out=None):
+    """uint8 images viewed as [N][C][S][S] through any strides (a CHW dataset, or the permuted view
+    of HWC bytes) as planar float32 (rgan_swd_load_u8)."""
+    L.require_cuda(x)
+    if x.dtype != torch.uint8 or x.dim() != 4 or x.shape[2] != x.shape[3] or x.numel() == 0 or min(x.stride()) < 0:
+        raise L.RganError(f"swd_load_u8: needs a uint8 [N][C][S][S] view, got {x.dtype} {tuple(x.shape)}")
+    N, C, S, _ = x.shape
+    out = torch.empty((N, C, S, S), dtype=torch.float32, device=x.device) if out is None else out
+    _f32c("swd_load_u8", out)
+    if out.numel() != x.numel():
+        raise L.RganError("swd_load_u8: out has another size")
+    strides = (ctypes.c_longlong * 4)(*x.stride())
+    L.check(L.lib().rgan_swd_load_u8(L.ptr(x), N, C, S, ctypes.cast(strides, ctypes.c_void_p), L.ptr(out),
+                                     L.stream()), "rgan_swd_load_u8")
+    return out
+
+
+def swd_pyr_down(x):
+    """The next Gaussian-pyramid level of planar images (rgan_swd_pyr_down): half the side."""
+    N, C, S = _swd_images("swd_pyr_down", x)
+    out = torch.empty((N, C, S // 2, S // 2), dtype=torch.float32, device=x.device)
+    L.check(L.lib().rgan_swd_pyr_down(L.ptr(x), N, C, S, L.ptr(out), L.stream()), "rgan_swd_pyr_down")
+    return out
+
+
+def swd_laplace(fine, coarse, out=None):
+    """fine - up(coarse) (rgan_swd_laplace); ``out`` may be ``fine``."""
+    N, C, S = _swd_images("swd_laplace", fine)
+    out = torch.empty_like(fine) if out is None else out
+    _f32c("swd_laplace", coarse, out)
+    if tuple(coarse.shape) != (N, C, S // 2, S // 2) or out.shape != fine.shape:
+        raise L.RganError(f"swd_laplace: coarse {tuple(coarse.shape)} / out do not go with fine {tuple(fine.shape)}")
+    L.check(L.lib().rgan_swd_laplace(L.ptr(fine), L.ptr(coarse), N, C, S, L.ptr(out), L.stream()), "rgan_swd_laplace")
+    return out
+
+
+def swd_positions(u, side):
+    """Patch centres 3 + floor(u (side - 6)) as int32, u uniform draws in [0, 1) (rgan_swd_positions)."""
+    _f32c("swd_positions", u)
+    pos = torch.empty(u.shape, dtype=torch.int32, device=u.device)
+    L.check(L.lib().rgan_swd_positions(L.ptr(u), u.numel(), int(side), L.ptr(pos), L.stream()), "rgan_swd_positions")
+    return pos
+
+
+def swd_descriptors(img, pos, desc, part):
+    """The 7x7xC patches of ``img`` [N][C][S][S] around ``pos`` [N][P][2] (int32 y, x) into the rows
+    ``desc`` [N P][49 C], and the images' double {sum, sum of squares} per channel into ``part``
+    [N][C][2] (rgan_swd_descriptors); desc and part may be slices of larger buffers."""
+    N, C, S = _swd_images("swd_descriptors", img)
+    L.require_cuda(pos, desc, part)
+    if pos.dtype != torch.int32 or not pos.is_contiguous() or pos.dim() != 3 or pos.shape[0] != N or pos.shape[2] != 2:
+        raise L.RganError(f"swd_descriptors: pos must be contiguous int32 [N][P][2], got {tuple(pos.shape)}")
+    P = int(pos.shape[1])
+    _f32c("swd_descriptors", desc)
+    if tuple(desc.shape) != (N * P, 49 * C):
+        raise L.RganError(f"swd_descriptors: desc must be [{N * P}][{49 * C}], got {tuple(desc.shape)}")
+    if part.dtype != torch.float64 or not part.is_contiguous() or tuple(part.shape) != (N, C, 2):
+        raise L.RganError(f"swd_descriptors: part must be contiguous float64 [{N}][{C}][2]")
+    L.check(L.lib().rgan_swd_descriptors(L.ptr(img), N, C, S, P, L.ptr(pos), L.ptr(desc), L.ptr(part), L.stream()),
+            "rgan_swd_descriptors")
+
+
+def swd_normalize(desc, part):
+    """``desc`` [M][49 C] normalised per channel in place with the statistics of ``part``
+    [nparts][C][2]; returns them, float64 [C][2] {mean, std}, on the device (rgan_swd_normalize)."""
+    _f32c("swd_normalize", desc)
+    L.require_cuda(part)
+    if part.dtype != torch.float64 or not part.is_contiguous() or part.dim() != 3 or part.shape[2] != 2:
+        raise L.RganError("swd_normalize: part must be contiguous float64 [nparts][C][2]")
+    nparts, C = int(part.shape[0]), int(part.shape[1])
+    if desc.dim() != 2 or desc.shape[1] != 49 * C or desc.numel() == 0 or nparts == 0:
+        raise L.RganError(f"swd_normalize: desc {tuple(desc.shape)} does not go with {C} channels")
+    stats = torch.empty((C, 2), dtype=torch.float64, device=desc.device)
+    L.check(L.lib().rgan_swd_normalize(L.ptr(desc), int(desc.shape[0]), C, L.ptr(part), nparts, L.ptr(stats),
+                                       L.stream()), "rgan_swd_normalize")
+    return stats
+
+
+def swd_unit_columns(dirs):
+    """``dirs`` [K][D] scaled in place to unit columns (rgan_swd_unit_columns)."""
+    _f32c("swd_unit_columns", dirs)
+    if dirs.dim() != 2 or dirs.numel() == 0:
+        raise L.RganError("swd_unit_columns: dirs must be [K][D]")
+    L.check(L.lib().rgan_swd_unit_columns(L.ptr(dirs), int(dirs.shape[0]), int(dirs.shape[1]), L.stream()),
+            "rgan_swd_unit_columns")
+    return dirs
+
+
+def swd_project(desc, dirs, out=None):
+    """proj [D][M] = (desc [M][K] dirs [K][D]) transposed, fp32 in ascending k (rgan_swd_project)."""
+    _f32c("swd_project", desc, dirs)
+    if desc.dim() != 2 or dirs.dim() != 2 or desc.shape[1] != dirs.shape[0] or desc.numel() == 0 or dirs.numel() == 0:
+        raise L.RganError(f"swd_project: desc {tuple(desc.shape)} and dirs {tuple(dirs.shape)} do not go together")
+    M, K, D = int(desc.shape[0]), int(desc.shape[1]), int(dirs.shape[1])
+    out = torch.empty((D, M), dtype=torch.float32, device=desc.device) if out is None else out
+    _f32c("swd_project", out)
+    if out.numel() != D * M:
+        raise L.RganError("swd_project: out has another size")
+    L.check(L.lib().rgan_swd_project(L.ptr(desc), L.ptr(dirs), M, K, D, L.ptr(out), L.stream()), "rgan_swd_project")
+    return out
+
+
+def swd_l1(a, b, out=None):
+    """sum |a - b| into ``out`` (a float64 device scalar or one-element view; rgan_swd_l1)."""
+    _f32c("swd_l1", a, b)
+    n = a.numel()
+    if n == 0 or n != b.numel() or n >= 2 ** 31:
+        raise L.RganError("swd_l1: a and b must hold the same 1 <= n < 2^31 elements")
+    out = torch.empty(1, dtype=torch.float64, device=a.device) if out is None else out
+    if out.dtype != torch.float64 or out.numel() != 1 or not out.is_cuda:
+        raise L.RganError("swd_l1: out must be one float64 on the device")
+    nbytes = L.lib().rgan_swd_l1_ws_bytes(n)
+    ws = L.workspace(nbytes, a.device)
+    L.check(L.lib().rgan_swd_l1(L.ptr(a), L.ptr(b), n, L.ptr(out), L.ptr(ws), nbytes, L.stream()), "rgan_swd_l1")
+    return out

@@ -32,6 +32,16 @@ dispatcher-level tracers see the MI355X kernels as graph nodes (not opaque Pytho
   rgan::ada_update_     rank statistic of a D step and the controller of p (--rgan_ada_target, mutating)
   rgan::lecam_           LeCam term of a D step, its gradients and the move of its anchors (--rgan_lecam, mutating; not in the reference)
   rgan::lecam_finish_    the same from the ranks' summed partial sums (data parallel, mutating)
+  rgan::sort_segments    rows of fp32 keys sorted ascending, LSD radix sort (the sliced Wasserstein metric's; not in the reference)
+  rgan::swd_load_u8      the metric's steps (--rgan_swd_every, evaluate; not in the reference): u8 images to planar fp32,
+  rgan::swd_pyr_down     a Gaussian-pyramid level,
+  rgan::swd_laplace      a Laplacian-pyramid level,
+  rgan::swd_positions    patch centres from uniform draws,
+  rgan::swd_descriptors_ 7x7xC patches and their channel sums (mutating),
+  rgan::swd_normalize_   their per-channel normalisation (mutating),
+  rgan::swd_unit_columns_ unit projection directions (mutating),
+  rgan::swd_project      the projections, direction-major,
+  rgan::swd_l1           sum |a - b| in double
   rgan::adam_            torch.optim.Adam's single-tensor step (mutating)          GLI:659,712
   rgan::ema_update_      moving average of G's weights (--rgan_ema_G, mutating; not in the reference)
 
@@ -713,6 +723,120 @@ def _(sums, n_global, sides, hyper, state, loss):
     return None
 
 
+# ------------------------------------------------------------------ segmented sort, sliced Wasserstein distance
+@torch.library.custom_op("rgan::sort_segments", mutates_args=(), device_types=_DEV)
+def sort_segments(x: torch.Tensor) -> torch.Tensor:
+    """Each row of x [nseg][len] sorted ascending in the total order of the fp32 bit patterns
+    (include/rgan.h rgan_sort_segments)."""
+    return K.sort_segments(x)
+
+
+@sort_segments.register_fake
+def _(x):
+    return torch.empty_like(x)
+
+
+@torch.library.custom_op("rgan::swd_load_u8", mutates_args=(), device_types=_DEV)
+def swd_load_u8(x: torch.Tensor) -> torch.Tensor:
+    """A uint8 [N][C][S][S] view of any strides as planar float32 (rgan_swd_load_u8)."""
+    return K.swd_load_u8(x)
+
+
+@swd_load_u8.register_fake
+def _(x):
+    return torch.empty(x.shape, dtype=torch.float32, device=x.device)
+
+
+@torch.library.custom_op("rgan::swd_pyr_down", mutates_args=(), device_types=_DEV)
+def swd_pyr_down(x: torch.Tensor) -> torch.Tensor:
+    """The next Gaussian-pyramid level, half the side (rgan_swd_pyr_down)."""
+    return K.swd_pyr_down(x)
+
+
+@swd_pyr_down.register_fake
+def _(x):
+    N, C, S, _ = x.shape
+    return torch.empty((N, C, S // 2, S // 2), dtype=torch.float32, device=x.device)
+
+
+@torch.library.custom_op("rgan::swd_laplace", mutates_args=(), device_types=_DEV)
+def swd_laplace(fine: torch.Tensor, coarse: torch.Tensor) -> torch.Tensor:
+    """fine - up(coarse), a Laplacian-pyramid level (rgan_swd_laplace)."""
+    return K.swd_laplace(fine, coarse)
+
+
+@swd_laplace.register_fake
+def _(fine, coarse):
+    return torch.empty_like(fine)
+
+
+@torch.library.custom_op("rgan::swd_positions", mutates_args=(), device_types=_DEV)
+def swd_positions(u: torch.Tensor, side: int) -> torch.Tensor:
+    """Patch centres 3 + floor(u (side - 6)), int32 (rgan_swd_positions)."""
+    return K.swd_positions(u, side)
+
+
+@swd_positions.register_fake
+def _(u, side):
+    return torch.empty(u.shape, dtype=torch.int32, device=u.device)
+
+
+@torch.library.custom_op("rgan::swd_descriptors_", mutates_args=("desc", "part"), device_types=_DEV)
+def swd_descriptors_(img: torch.Tensor, pos: torch.Tensor, desc: torch.Tensor, part: torch.Tensor) -> None:
+    """7x7xC patches of img around pos into the rows desc, the per-image channel sums into part
+    (rgan_swd_descriptors)."""
+    K.swd_descriptors(img, pos, desc, part)
+
+
+@swd_descriptors_.register_fake
+def _(img, pos, desc, part):
+    return None
+
+
+@torch.library.custom_op("rgan::swd_normalize_", mutates_args=("desc",), device_types=_DEV)
+def swd_normalize_(desc: torch.Tensor, part: torch.Tensor) -> torch.Tensor:
+    """desc normalised per channel in place; returns float64 [C][2] {mean, std} (rgan_swd_normalize)."""
+    return K.swd_normalize(desc, part)
+
+
+@swd_normalize_.register_fake
+def _(desc, part):
+    return torch.empty((part.shape[1], 2), dtype=torch.float64, device=desc.device)
+
+
+@torch.library.custom_op("rgan::swd_unit_columns_", mutates_args=("dirs",), device_types=_DEV)
+def swd_unit_columns_(dirs: torch.Tensor) -> None:
+    """dirs [K][D] scaled to unit columns in place (rgan_swd_unit_columns)."""
+    K.swd_unit_columns(dirs)
+
+
+@swd_unit_columns_.register_fake
+def _(dirs):
+    return None
+
+
+@torch.library.custom_op("rgan::swd_project", mutates_args=(), device_types=_DEV)
+def swd_project(desc: torch.Tensor, dirs: torch.Tensor) -> torch.Tensor:
+    """proj [D][M] of desc [M][K] on dirs [K][D] (rgan_swd_project)."""
+    return K.swd_project(desc, dirs)
+
+
+@swd_project.register_fake
+def _(desc, dirs):
+    return torch.empty((dirs.shape[1], desc.shape[0]), dtype=torch.float32, device=desc.device)
+
+
+@torch.library.custom_op("rgan::swd_l1", mutates_args=(), device_types=_DEV)
+def swd_l1(a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
+    """sum |a - b| as float64 [1] (rgan_swd_l1)."""
+    return K.swd_l1(a, b)
+
+
+@swd_l1.register_fake
+def _(a, b):
+    return torch.empty(1, dtype=torch.float64, device=a.device)
+
+
 # ------------------------------------------------------------------ traced layers (nets)
 def tracing(t):
     """A trace (torch.export / torch.compile / fake-tensor propagation) rather than a run."""
@@ -746,4 +870,6 @@ OPS = ("conv2d", "conv2d_dgrad", "conv2d_wgrad", "channel_sum", "act_backward", 
        "batch_norm_apply", "batch_norm_backward", "spectral_power_", "spectral_scale", "spectral_backward", "loss_head",
        "loss_head_grad", "gp_penalty", "gp_penalty_backward", "gp_zc_penalty", "gp_zc_penalty_backward", "diffaug",
        "diffaug_backward", "diffaug_p", "diffaug_p_backward", "adam_", "ema_update_", "ada_update_", "lecam_",
-       "lecam_finish_", "diffaug_geo", "diffaug_geo_backward")
+       "lecam_finish_", "diffaug_geo", "diffaug_geo_backward", "sort_segments", "swd_load_u8", "swd_pyr_down",
+       "swd_laplace", "swd_positions", "swd_descriptors_", "swd_normalize_", "swd_unit_columns_", "swd_project",
+       "swd_l1")

@@ -632,6 +632,25 @@ def generate_extra_images(G, p, folder, device="cuda"):
             ext_curr += 100
 
 
+def make_swd(p, images):
+    """The sliced Wasserstein metric of --rgan_swd_every over the training images (its centres and
+    directions drawn once, the real set's descriptors cached), or None when the flag is off."""
+    from .config import validate_swd
+    if not validate_swd(p.rgan_swd_every, p.rgan_swd_images, p.image_size, world=dp.world()):
+        return None
+    from .swd import SlicedWasserstein
+    return SlicedWasserstein(images, p, n_images=p.rgan_swd_images, seed=p.seed)
+
+
+def swd_line(metric, t, p):
+    """One evaluation of the trainer's generator (the averaged one with --rgan_ema_G), after the
+    queued training work; G's buffers are put back, and z is the metric's own stream, so the
+    training state is what it was."""
+    from .swd import format_line
+    t.flush()
+    return format_line(metric.evaluate(t.G if t.ema is None else t.ema.generator(), p.z_size))
+
+
 def main(argv=None):
     from .images import save_image
     p = parse(argv)
@@ -662,6 +681,7 @@ def main(argv=None):
         say(f"Resumed from iteration {current_set_images * p.gen_every}.")
     say(t.G)
     say(t.D)
+    metric = make_swd(p, images)
     meter = ThroughputMeter(t) if p.rgan_perf_log else None
     if meter is not None:
         meter.tick(iter_offset, time.time())
@@ -699,6 +719,10 @@ def main(argv=None):
                 perf = meter.tick(i + 1, time.time())
                 if perf:
                     say(perf)
+        if metric is not None and (i + 1) % p.rgan_swd_every == 0:
+            t_out = output_clock()
+            say(f"[{i}] " + swd_line(metric, t, p))
+            output_done(t_out)
         if (i + 1) % p.gen_every == 0:
             t_out = output_clock()
             current_set_images += 1
