@@ -31,7 +31,8 @@ extern "C" {
  * rgan_diffaug_workspace, rgan_diffaug, rgan_ema_update, rgan_diffaug_p, rgan_ada_update,
  * rgan_ada_adjust, rgan_lecam, rgan_lecam_finish, rgan_diffaug_geo_workspace and rgan_diffaug_geo
  * are additive within revision 4 (nothing else changed), and so are rgan_sort_segments with its
- * _tile and _ws_bytes and the rgan_swd_ entry points. */
+ * _tile and _ws_bytes, the rgan_swd_ entry points and the nearest-image entry points
+ * (rgan_nn_row_bytes, _pack_u8, _topk_splits, _topk_ws_bytes, _topk, _covered). */
 #define RGAN_ABI_VERSION 4
 
 /* Activation codes fused into epilogues (GLI:345,370,388,417,437,450; SELU GLI:338). */
@@ -761,6 +762,54 @@ int rgan_swd_project(const float* desc, const float* dirs, int M, int K, int D, 
 size_t rgan_swd_l1_ws_bytes(long long n);
 int rgan_swd_l1(const float* a, const float* b, long long n, double* out, void* ws, size_t ws_bytes,
                 void* stream);
+
+/* ---- nearest training images and k-NN precision / recall in pixel space (csrc/nn.hip;
+ * --rgan_nn_every, evaluate --rgan_nn; Kynkaanniemi et al., NeurIPS 2019; no counterpart in the
+ * reference) ----
+ * (additive within ABI revision 4: no existing entry point changed)
+ * All arithmetic is integer and exact: equal inputs give equal outputs whatever the tiling or the
+ * number of parts.  Every entry point refuses (RGAN_EINVAL, nothing launched) a null pointer, a size
+ * < 1 and what its own lines add.
+ *
+ * A descriptor row is row_bytes int8: D = C s s values in (c, y, x) order, then zeros up to the next
+ * multiple of 64.  rgan_nn_row_bytes(C, s) is that size, or 0 for what is refused: C outside 1..4,
+ * s not in {8, 16, 32, 64}, or more than RGAN_NN_MAX_ROW_BYTES = 12288 bytes (so that a squared
+ * distance, at most 255^2 12288 = 799 027 200, and every norm and dot product fit int32).
+ *
+ * rgan_nn_pack_u8: image n < N of in (uint8, element (n, c, y, x) at n s0 + c s1 + y s2 + x s3,
+ * strides = host long long[4], each >= 0: CHW sets and HWC bytes alike) -> desc[n][row_bytes] and
+ * norm[n].  With f = S / s (S % s == 0, 1 <= f <= 32) a descriptor value is
+ * (sum of the f x f box + f f / 2) / (f f) - 128, the box mean with halves rounded up, shifted into
+ * int8; norm[n] = the sum of the squared shifted values.  The pad bytes are written as 0.
+ *
+ * rgan_nn_topk: for query row q < Q of a (norms na) the k (1..8) nearest of the R rows of b (norms
+ * nb): the k smallest keys (uint64(d2) << 32) | r, d2 = na[q] + nb[r] - 2 a[q].b[r], over the r
+ * with r - q != self_offset (RGAN_NN_NO_SELF excludes nothing; self_offset = lo is leave-one-out
+ * when a is rows lo.. of b).  dist[q][j], idx[q][j] ascend in j, ties by the smaller r; when fewer
+ * than k rows remain the tail is dist = INT32_MAX, idx = -1.  a and b are 16-byte aligned, row_bytes
+ * a multiple of 64 and <= 12288.  The rows of b are cut into nsplit contiguous parts (part p is
+ * rows [p R / nsplit, (p + 1) R / nsplit); 0 = rgan_nn_topk_splits(Q, R), at most 4096), a block
+ * takes 128 queries and one part and writes its k best keys to ws, and a second kernel merges the
+ * parts; keys are distinct, so the result is the same for every nsplit.  ws: 8-byte aligned,
+ * rgan_nn_topk_ws_bytes(Q, R, k, nsplit) bytes (0 for refused sizes; Q nsplit k must fit int).
+ * The products come from v_mfma_i32_32x32x32_i8 over LDS tiles of 128 rows x 128 bytes.
+ *
+ * rgan_nn_covered: flag[q] = 1 when some r with r - q != self_offset has d2(q, r) <= radius[r],
+ * else 0 (flag is zeroed on the stream first, then blocks that found one store 1: the same GEMM
+ * body with another epilogue). */
+#define RGAN_NN_MAX_ROW_BYTES 12288
+#define RGAN_NN_NO_SELF (-0x7fffffffffffffffLL - 1)
+size_t rgan_nn_row_bytes(int C, int s);
+int rgan_nn_pack_u8(const uint8_t* in, int N, int C, int S, const long long* strides, int s,
+                    int8_t* desc, int* norm, void* stream);
+int rgan_nn_topk_splits(int Q, int R);
+size_t rgan_nn_topk_ws_bytes(int Q, int R, int k, int nsplit);
+int rgan_nn_topk(const int8_t* a, const int* na, int Q, const int8_t* b, const int* nb, int R,
+                 int row_bytes, int k, long long self_offset, int nsplit, int* dist, int* idx, void* ws,
+                 size_t ws_bytes, void* stream);
+int rgan_nn_covered(const int8_t* a, const int* na, int Q, const int8_t* b, const int* nb,
+                    const int* radius, int R, int row_bytes, long long self_offset, int* flag,
+                    void* stream);
 
 #ifdef __cplusplus
 }

@@ -158,6 +158,13 @@ _SIGS = {
     "rgan_swd_project": (c_int, [c_vp, c_vp, c_int, c_int, c_int, c_vp, c_vp]),
     "rgan_swd_l1_ws_bytes": (c_sz, [c_ll]),
     "rgan_swd_l1": (c_int, [c_vp, c_vp, c_ll, c_vp, c_vp, c_sz, c_vp]),
+    "rgan_nn_row_bytes": (c_sz, [c_int, c_int]),
+    "rgan_nn_pack_u8": (c_int, [c_vp, c_int, c_int, c_int, c_vp, c_int, c_vp, c_vp, c_vp]),
+    "rgan_nn_topk_splits": (c_int, [c_int, c_int]),
+    "rgan_nn_topk_ws_bytes": (c_sz, [c_int, c_int, c_int, c_int]),
+    "rgan_nn_topk": (c_int, [c_vp, c_vp, c_int, c_vp, c_vp, c_int, c_int, c_int, c_ll, c_int, c_vp, c_vp, c_vp, c_sz,
+                             c_vp]),
+    "rgan_nn_covered": (c_int, [c_vp, c_vp, c_int, c_vp, c_vp, c_vp, c_int, c_int, c_ll, c_vp, c_vp]),
     "rgan_set_gemm_emulation": (c_int, [c_int]),
     "rgan_profile_begin": (c_int, [c_int]),
     "rgan_profile_end": (c_int, [c_vp, c_vp, c_vp]),

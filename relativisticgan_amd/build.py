@@ -25,7 +25,7 @@ FLAGS = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-I" + os.path.
 SOURCES = ["gemm_wgrad.hip", "gemm_conv.hip", "conv_narrow.hip", "gemm_convt2.hip", "bn_act.hip", "augment_geo.hip",
            "first_layer.hip", "conv_pack.hip", "conv_reduce.hip", "heads_optim.hip", "conv_gemm.hip", "conv_plan.hip",
            "conv_prof.hip", "images.hip", "augment.hip", "ema.hip", "sampling.hip", "patches.hip", "upsample.hip",
-           "gp_zc.hip", "ada.hip", "lecam.hip", "swd.hip", "sort.hip"]
+           "gp_zc.hip", "ada.hip", "lecam.hip", "swd.hip", "sort.hip", "nn.hip"]
 
 
 def _stale(obj, src):

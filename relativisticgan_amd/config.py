@@ -20,7 +20,10 @@ distance of D's outputs from moving averages of its outputs on the other kind of
 the D step without another pass of D; 0 = off, the default; see ``validate_lecam``),
 ``--rgan_swd_every K`` with ``--rgan_swd_images N`` (log the sliced Wasserstein distance between
 the training images and G's samples after every K-th iteration; 0 = off, the default;
-single-process runs only, see ``validate_swd``; relativisticgan_amd/swd.py), ``--rgan_pac 2``
+single-process runs only, see ``validate_swd``; relativisticgan_amd/swd.py), ``--rgan_nn_every K`` /
+``--rgan_nn True`` with ``--rgan_nn_images``, ``--rgan_nn_side`` and ``--rgan_nn_k`` (each generated
+image's nearest training images as a grid, and k-NN precision / recall in pixel space, during
+training / in evaluate; off by default; see ``validate_nn``; relativisticgan_amd/neighbours.py), ``--rgan_pac 2``
 (the PacGAN-2 script, code/GAN_losses_iter_PAC.py, which shares this CLI) and
 ``--rgan_script`` (the defaults of GAN_losses_iter / GAN_losses_iter_art / GAN_losses_iter_PAC).
 """
@@ -60,6 +63,8 @@ SCRIPTS = ("GAN_losses_iter", "GAN_losses_iter_art", "GAN_losses_iter_PAC")
 
 
 LECAM_DEFAULTS = (0.99, 1)  # --rgan_lecam_beta, --rgan_lecam_start
+NN_DEFAULTS = (8192, 64, 3)  # --rgan_nn_images, --rgan_nn_side, --rgan_nn_k
+NN_SIDES = (8, 16, 32, 64)
 
 
 def make_parser(script="GAN_losses_iter"):
@@ -141,6 +146,23 @@ def make_parser(script="GAN_losses_iter"):
     p.add_argument("--rgan_swd_images", type=int, default=8192,
                    help="images per set for the sliced Wasserstein distance (--rgan_swd_every and "
                         "python -m relativisticgan_amd.evaluate), at most the dataset's size (default 8192)")
+    p.add_argument("--rgan_nn_every", type=int, default=0,
+                   help="after every K-th iteration, log the nearest-training-image line (median RMS pixel "
+                        "difference of G's samples to their nearest training image, the same among the training "
+                        "images, their ratio, and k-NN precision / recall; Kynkaanniemi et al., NeurIPS 2019, in "
+                        "pixel space) and write images/nn_iterNNNNN.png, 8 samples next to their nearest training "
+                        "images; single-process runs only (default 0: off)")
+    p.add_argument("--rgan_nn", type="bool", default=False,
+                   help="python -m relativisticgan_amd.evaluate: also print that line and write nn.png into "
+                        "--output_folder (default False)")
+    p.add_argument("--rgan_nn_images", type=int, default=NN_DEFAULTS[0],
+                   help="training and generated images compared by --rgan_nn_every / --rgan_nn, at most the "
+                        "dataset's size (default 8192)")
+    p.add_argument("--rgan_nn_side", type=int, default=NN_DEFAULTS[1],
+                   help="side to which images are box-averaged before they are compared: 8, 16, 32 or 64, a "
+                        "divisor of --image_size (default 64)")
+    p.add_argument("--rgan_nn_k", type=int, default=NN_DEFAULTS[2],
+                   help="neighbours per image, 1..8: the grid's columns and the k of precision / recall (default 3)")
     p.add_argument("--rgan_synthetic", type=int, default=0,
                    help="use N synthetic images instead of an image folder (no torchvision here)")
     return p
@@ -164,6 +186,7 @@ def parse(argv=None):
         validate_ada(ns.rgan_diffaug, ns.rgan_aug_p, ns.rgan_ada_target, ns.rgan_ada_interval, ns.rgan_ada_kimg)
         validate_lecam(ns.rgan_lecam, ns.rgan_lecam_beta, ns.rgan_lecam_start)
         validate_swd(ns.rgan_swd_every, ns.rgan_swd_images, ns.image_size)
+        validate_nn(ns.rgan_nn_every, ns.rgan_nn, ns.rgan_nn_images, ns.rgan_nn_side, ns.rgan_nn_k, ns.image_size)
     except ValueError as e:
         parser.error(str(e))
     return ns
@@ -186,6 +209,33 @@ def validate_swd(every, images=8192, image_size=64, world=None):
     if world > 1:
         raise ValueError("--rgan_swd_every is for single-process runs: under data parallelism evaluate a checkpoint "
                          "with python -m relativisticgan_amd.evaluate instead")
+    return True
+
+
+def validate_nn(every=0, on=False, images=NN_DEFAULTS[0], side=NN_DEFAULTS[1], k=NN_DEFAULTS[2], image_size=64,
+                world=None):
+    """Check --rgan_nn_every / --rgan_nn / --rgan_nn_images / --rgan_nn_side / --rgan_nn_k (ValueError
+    otherwise); True when the check is on.  The working side is min(side, image_size).  Refused
+    under data parallelism (WORLD_SIZE > 1) for the reason ``validate_swd`` gives."""
+    import os
+    if every < 0:
+        raise ValueError(f"--rgan_nn_every must be >= 0 (0 = off), got {every}")
+    if not 1 <= k <= 8:
+        raise ValueError(f"--rgan_nn_k must lie in 1..8, got {k}")
+    if images < k + 1:
+        raise ValueError(f"--rgan_nn_images must be >= --rgan_nn_k + 1 = {k + 1}, got {images}")
+    if side not in NN_SIDES:
+        raise ValueError(f"--rgan_nn_side must be one of 8, 16, 32, 64, got {side}")
+    if every == 0 and not on:
+        return False
+    s = min(side, image_size)
+    if s not in NN_SIDES or image_size % s or image_size // s > 32:
+        raise ValueError(f"--rgan_nn_side {side} needs an --image_size it divides by at most 32 (or a smaller one in "
+                         f"8, 16, 32, 64), got {image_size}")
+    world = int(os.environ.get("WORLD_SIZE", "1")) if world is None else world
+    if world > 1:
+        raise ValueError("--rgan_nn_every / --rgan_nn are for single-process runs: under data parallelism evaluate a "
+                         "checkpoint with python -m relativisticgan_amd.evaluate --rgan_nn True instead")
     return True
 
 

@@ -11,7 +11,17 @@ quantises them, and prints one line::
 one value per Laplacian-pyramid level (named by its side) and their average
 (relativisticgan_amd/swd.py; the reference's own quality number is FID, code/fid.py, which needs
 TensorFlow and a downloaded network).  N = min(--rgan_swd_images, the number of real images).
+
+With ``--rgan_nn True`` [--rgan_nn_images N] [--rgan_nn_side s] [--rgan_nn_k k] a second line follows::
+
+    NN s64 k3  fake->real: a  real->real: b  ratio: c  precision: d  recall: e
+
+(relativisticgan_amd/neighbours.py: the median RMS pixel difference of a generated image to its
+nearest training image, the same among the training images, their ratio, and k-NN precision and
+recall in pixel space), and ``nn.png`` is written into ``--output_folder``: 8 generated images,
+each next to its k nearest training images.
 """
+import os
 import sys
 
 import torch
@@ -41,9 +51,24 @@ def main(argv=None):
     else:
         G.load_state_dict(ck["G_state"])
     G.to("cuda")
-    metric = SlicedWasserstein(load_images(p), p, n_images=p.rgan_swd_images, seed=p.seed)
+    metric_images = load_images(p)
+    metric = SlicedWasserstein(metric_images, p, n_images=p.rgan_swd_images, seed=p.seed)
     result = metric.evaluate(G, p.z_size, keep_buffers=False)
     print(format_line(result), flush=True)
+    if p.rgan_nn:
+        from .config import validate_nn
+        from .images import write_png
+        from .neighbours import NearestNeighbours, format_line as nn_format_line
+        try:
+            validate_nn(0, True, p.rgan_nn_images, p.rgan_nn_side, p.rgan_nn_k, p.image_size)
+        except ValueError as e:
+            raise SystemExit(str(e))
+        check = NearestNeighbours(metric_images, p, n_images=p.rgan_nn_images, side=p.rgan_nn_side, k=p.rgan_nn_k,
+                                  seed=p.seed)
+        nn_result, grid = check.evaluate(G, p.z_size, keep_buffers=False, with_grid=True)
+        print(nn_format_line(nn_result, check.s, check.k), flush=True)
+        os.makedirs(p.output_folder, exist_ok=True)
+        write_png(os.path.join(p.output_folder, "nn.png"), grid.cpu())
     return result
 
 

@@ -1516,3 +1516,88 @@ def swd_l1(a, b, out=None):
     ws = L.workspace(nbytes, a.device)
     L.check(L.lib().rgan_swd_l1(L.ptr(a), L.ptr(b), n, L.ptr(out), L.ptr(ws), nbytes, L.stream()), "rgan_swd_l1")
     return out
+
+
+# ------------------------------------------------------------------ nearest training images
+NN_NO_SELF = -2 ** 63  # RGAN_NN_NO_SELF: no reference is excluded
+
+
+def nn_row_bytes(C, s):
+    """Bytes of a descriptor row of ``C`` channels at working side ``s`` (rgan_nn_row_bytes): C s s
+    rounded up to a multiple of 64; refuses C outside 1..4, s not in {8, 16, 32, 64} and > 12288."""
+    n = int(L.lib().rgan_nn_row_bytes(int(C), int(s)))
+    if n == 0:
+        raise L.RganError(f"nn_row_bytes: no descriptor for {C} channels at side {s} (1 <= C <= 4, side in "
+                          "{8, 16, 32, 64}, at most 12288 bytes)")
+    return n
+
+
+def nn_pack_u8(x, s):
+    """uint8 images viewed as [N][C][S][S] through any strides -> ``(desc, norm)``: int8
+    [N][row_bytes] box-mean descriptors at side ``s`` and their int32 squared norms (rgan_nn_pack_u8)."""
+    L.require_cuda(x)
+    if x.dtype != torch.uint8 or x.dim() != 4 or x.shape[2] != x.shape[3] or x.numel() == 0 or min(x.stride()) < 0:
+        raise L.RganError(f"nn_pack_u8: needs a uint8 [N][C][S][S] view, got {x.dtype} {tuple(x.shape)}")
+    N, C, S, _ = (int(v) for v in x.shape)
+    s = int(s)
+    row_bytes = nn_row_bytes(C, s)
+    if S % s or S // s > 32:
+        raise L.RganError(f"nn_pack_u8: side {s} must divide the image side {S}, by at most 32")
+    desc = torch.empty((N, row_bytes), dtype=torch.int8, device=x.device)
+    norm = torch.empty(N, dtype=torch.int32, device=x.device)
+    strides = (ctypes.c_longlong * 4)(*x.stride())
+    L.check(L.lib().rgan_nn_pack_u8(L.ptr(x), N, C, S, ctypes.cast(strides, ctypes.c_void_p), s, L.ptr(desc),
+                                    L.ptr(norm), L.stream()), "rgan_nn_pack_u8")
+    return desc, norm
+
+
+def _nn_operands(what, a, na, b, nb):
+    L.require_cuda(a, na, b, nb)
+    for d, n in ((a, na), (b, nb)):
+        if (d.dtype != torch.int8 or d.dim() != 2 or not d.is_contiguous() or d.numel() == 0
+                or n.dtype != torch.int32 or not n.is_contiguous() or tuple(n.shape) != (d.shape[0],)):
+            raise L.RganError(f"{what}: needs contiguous int8 [rows][row_bytes] descriptors with int32 [rows] norms")
+    if a.shape[1] != b.shape[1]:
+        raise L.RganError(f"{what}: row sizes {a.shape[1]} and {b.shape[1]} differ")
+    return int(a.shape[0]), int(b.shape[0]), int(a.shape[1])
+
+
+def nn_topk(a, na, b, nb, k, self_offset=None, nsplit=0, out=None):
+    """``(dist, idx)``, int32 [Q][k]: for each row of ``a`` the ``k`` nearest rows of ``b`` by exact
+    squared distance, ties to the smaller index; row ``q + self_offset`` of b is left out
+    (``None``: none is).  ``nsplit``: parts of b, 0 = automatic; the result does not depend on it.
+    ``out``: a (dist, idx) pair of contiguous int32 [Q][k] views to write (rgan_nn_topk)."""
+    Q, R, row_bytes = _nn_operands("nn_topk", a, na, b, nb)
+    k, nsplit = int(k), int(nsplit)
+    if out is None:
+        dist = torch.empty((Q, k), dtype=torch.int32, device=a.device)
+        idx = torch.empty((Q, k), dtype=torch.int32, device=a.device)
+    else:
+        dist, idx = out
+        L.require_cuda(dist, idx)
+        for t in (dist, idx):
+            if t.dtype != torch.int32 or not t.is_contiguous() or tuple(t.shape) != (Q, k):
+                raise L.RganError(f"nn_topk: out must be two contiguous int32 [{Q}][{k}] tensors")
+    nbytes = L.lib().rgan_nn_topk_ws_bytes(Q, R, k, nsplit)
+    ws = L.workspace(nbytes, a.device)
+    self_offset = NN_NO_SELF if self_offset is None else int(self_offset)
+    L.check(L.lib().rgan_nn_topk(L.ptr(a), L.ptr(na), Q, L.ptr(b), L.ptr(nb), R, row_bytes, k, self_offset, nsplit,
+                                 L.ptr(dist), L.ptr(idx), L.ptr(ws), nbytes, L.stream()), "rgan_nn_topk")
+    return dist, idx
+
+
+def nn_covered(a, na, b, nb, radius, self_offset=None, out=None):
+    """int32 [Q]: 1 where a row of ``a`` lies within ``radius[r]`` (int32 [R], squared, equality
+    counts) of some row r of ``b`` other than ``q + self_offset``, else 0 (rgan_nn_covered)."""
+    Q, R, row_bytes = _nn_operands("nn_covered", a, na, b, nb)
+    L.require_cuda(radius)
+    if radius.dtype != torch.int32 or not radius.is_contiguous() or tuple(radius.shape) != (R,):
+        raise L.RganError(f"nn_covered: radius must be contiguous int32 [{R}]")
+    flag = torch.empty(Q, dtype=torch.int32, device=a.device) if out is None else out
+    L.require_cuda(flag)
+    if flag.dtype != torch.int32 or not flag.is_contiguous() or tuple(flag.shape) != (Q,):
+        raise L.RganError(f"nn_covered: out must be contiguous int32 [{Q}]")
+    self_offset = NN_NO_SELF if self_offset is None else int(self_offset)
+    L.check(L.lib().rgan_nn_covered(L.ptr(a), L.ptr(na), Q, L.ptr(b), L.ptr(nb), L.ptr(radius), R, row_bytes,
+                                    self_offset, L.ptr(flag), L.stream()), "rgan_nn_covered")
+    return flag

@@ -42,6 +42,10 @@ dispatcher-level tracers see the MI355X kernels as graph nodes (not opaque Pytho
   rgan::swd_unit_columns_ unit projection directions (mutating),
   rgan::swd_project      the projections, direction-major,
   rgan::swd_l1           sum |a - b| in double
+  rgan::nn_pack_u8       the nearest-training-image check (--rgan_nn_every, evaluate --rgan_nn; not in the reference): u8
+                         images to int8 box-mean descriptors and their norms,
+  rgan::nn_topk          the k nearest rows by exact integer distance on the int8 matrix cores,
+  rgan::nn_covered       whether a row lies within some row's radius
   rgan::adam_            torch.optim.Adam's single-tensor step (mutating)          GLI:659,712
   rgan::ema_update_      moving average of G's weights (--rgan_ema_G, mutating; not in the reference)
 
@@ -837,6 +841,45 @@ def _(a, b):
     return torch.empty(1, dtype=torch.float64, device=a.device)
 
 
+@torch.library.custom_op("rgan::nn_pack_u8", mutates_args=(), device_types=_DEV)
+def nn_pack_u8(x: torch.Tensor, s: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    """A uint8 [N][C][S][S] view of any strides as int8 box-mean descriptors at side s and their int32
+    squared norms (rgan_nn_pack_u8)."""
+    return K.nn_pack_u8(x, s)
+
+
+@nn_pack_u8.register_fake
+def _(x, s):
+    row = (x.shape[1] * s * s + 63) // 64 * 64
+    return (torch.empty((x.shape[0], row), dtype=torch.int8, device=x.device),
+            torch.empty((x.shape[0],), dtype=torch.int32, device=x.device))
+
+
+@torch.library.custom_op("rgan::nn_topk", mutates_args=(), device_types=_DEV)
+def nn_topk(a: torch.Tensor, na: torch.Tensor, b: torch.Tensor, nb: torch.Tensor, k: int,
+            self_offset: Optional[int] = None, nsplit: int = 0) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(dist, idx) int32 [Q][k]: the k nearest rows of b for each row of a, exact (rgan_nn_topk)."""
+    return K.nn_topk(a, na, b, nb, k, self_offset, nsplit)
+
+
+@nn_topk.register_fake
+def _(a, na, b, nb, k, self_offset=None, nsplit=0):
+    return (torch.empty((a.shape[0], k), dtype=torch.int32, device=a.device),
+            torch.empty((a.shape[0], k), dtype=torch.int32, device=a.device))
+
+
+@torch.library.custom_op("rgan::nn_covered", mutates_args=(), device_types=_DEV)
+def nn_covered(a: torch.Tensor, na: torch.Tensor, b: torch.Tensor, nb: torch.Tensor, radius: torch.Tensor,
+               self_offset: Optional[int] = None) -> torch.Tensor:
+    """int32 [Q]: 1 where a row of a is within radius[r] of some row r of b (rgan_nn_covered)."""
+    return K.nn_covered(a, na, b, nb, radius, self_offset)
+
+
+@nn_covered.register_fake
+def _(a, na, b, nb, radius, self_offset=None):
+    return torch.empty((a.shape[0],), dtype=torch.int32, device=a.device)
+
+
 # ------------------------------------------------------------------ traced layers (nets)
 def tracing(t):
     """A trace (torch.export / torch.compile / fake-tensor propagation) rather than a run."""
@@ -872,4 +915,4 @@ OPS = ("conv2d", "conv2d_dgrad", "conv2d_wgrad", "channel_sum", "act_backward", 
        "diffaug_backward", "diffaug_p", "diffaug_p_backward", "adam_", "ema_update_", "ada_update_", "lecam_",
        "lecam_finish_", "diffaug_geo", "diffaug_geo_backward", "sort_segments", "swd_load_u8", "swd_pyr_down",
        "swd_laplace", "swd_positions", "swd_descriptors_", "swd_normalize_", "swd_unit_columns_", "swd_project",
-       "swd_l1")
+       "swd_l1", "nn_pack_u8", "nn_topk", "nn_covered")

@@ -651,6 +651,27 @@ def swd_line(metric, t, p):
     return format_line(metric.evaluate(t.G if t.ema is None else t.ema.generator(), p.z_size))
 
 
+def make_nn(p, images):
+    """The nearest-training-image check of --rgan_nn_every over the training images (their
+    descriptors packed once, their own neighbours cached), or None when the flag is off."""
+    from .config import validate_nn
+    if not validate_nn(p.rgan_nn_every, False, p.rgan_nn_images, p.rgan_nn_side, p.rgan_nn_k, p.image_size,
+                       world=dp.world()):
+        return None
+    from .neighbours import NearestNeighbours
+    return NearestNeighbours(images, p, n_images=p.rgan_nn_images, side=p.rgan_nn_side, k=p.rgan_nn_k, seed=p.seed)
+
+
+def nn_line(check, t, p):
+    """``(line, grid)`` of one evaluation of the trainer's generator (the averaged one with
+    --rgan_ema_G), after the queued training work; as in ``swd_line`` the training state is what it
+    was afterwards."""
+    from .neighbours import format_line
+    t.flush()
+    result, grid = check.evaluate(t.G if t.ema is None else t.ema.generator(), p.z_size, with_grid=True)
+    return format_line(result, check.s, check.k), grid
+
+
 def main(argv=None):
     from .images import save_image
     p = parse(argv)
@@ -682,6 +703,7 @@ def main(argv=None):
     say(t.G)
     say(t.D)
     metric = make_swd(p, images)
+    nn_check = make_nn(p, images)
     meter = ThroughputMeter(t) if p.rgan_perf_log else None
     if meter is not None:
         meter.tick(iter_offset, time.time())
@@ -722,6 +744,14 @@ def main(argv=None):
         if metric is not None and (i + 1) % p.rgan_swd_every == 0:
             t_out = output_clock()
             say(f"[{i}] " + swd_line(metric, t, p))
+            output_done(t_out)
+        if nn_check is not None and (i + 1) % p.rgan_nn_every == 0:
+            t_out = output_clock()
+            line, grid = nn_line(nn_check, t, p)
+            say(f"[{i}] " + line)
+            if lead:
+                from .images import write_png
+                write_png(os.path.join(base, "images", "nn_iter%05d.png" % i), grid.cpu())
             output_done(t_out)
         if (i + 1) % p.gen_every == 0:
             t_out = output_clock()
